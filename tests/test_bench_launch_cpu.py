@@ -27,7 +27,8 @@ def test_needs_launch_rules():
 
 def _run(args, extra_env=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env.update(YM_BENCH_RANKS_ONLY="1", MASTER_ADDR="127.0.0.1", **(extra_env or {}))
+    # gloo named outright: on a machine with a GPU the ranks would pick RCCL, which needs one device per rank
+    env.update(YM_BENCH_RANKS_ONLY="1", YM_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", **(extra_env or {}))
     return subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], env=env, capture_output=True, text=True,
                           timeout=240)
 
@@ -43,7 +44,7 @@ def test_gpus2_starts_two_ranks():
 def test_world_mismatch_fails_loudly():
     # a 2-rank job asked to report 3 GPUs: every rank exits non-zero instead of reporting 2 as 3
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env.update(YM_BENCH_RANKS_ONLY="1")
+    env.update(YM_BENCH_RANKS_ONLY="1", YM_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr=127.0.0.1", f"--master-port={bench.free_port()}", str(ROOT / "bench.py"),
                         "--gpus", "3"], env=env, capture_output=True, text=True, timeout=240)

@@ -5,10 +5,10 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-finA}; mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 500 python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 500 python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { echo "rocprof failed $?"; exit 1; }
+    python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { echo "rocprof failed $?"; exit 1; }
 KT=$(find $OUT/prof -name "*kernel_trace.csv" | head -1); KS=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
 NF=$(python3 -c "import csv,sys; print(sum(int(r['Calls']) for r in csv.DictReader(open('$KS')) if 'prep_weights' in r['Name']))")
 echo "forwards traced: $NF"

@@ -12,10 +12,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-prof04}; mkdir -p $OUT
 SRC=${2:-profiles/r04}
 export TMPDIR=/tmp
-timeout -k 10 400 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; tail -20 $OUT/bench.err; exit 1; }
 tail -1 $OUT/bench.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { echo "rocprof failed $?"; tail -5 $OUT/prof_bench.err; exit 1; }
+    python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/prof_bench.json 2> $OUT/prof_bench.err || { echo "rocprof failed $?"; tail -5 $OUT/prof_bench.err; exit 1; }
 KS=$(find $OUT/prof -name "*kernel_stats.csv" | head -1); KT=$(find $OUT/prof -name "*kernel_trace.csv" | head -1)
 NF=$(python3 -c "import csv; print(sum(int(r['Calls']) for r in csv.DictReader(open('$KS')) if 'prep_weights' in r['Name']))")
 echo "forwards traced: $NF"
@@ -34,7 +34,7 @@ timeout -k 10 300 python3 $R/tools/bn_bench.py > $OUT/bn_bench.txt 2> $OUT/bn.er
 tail -1 $OUT/bn_bench.txt
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/bpmc_$C -o run -- \
-      python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_$C.json 2> $OUT/bpmc_$C.err || { echo "bench pmc $C failed"; tail -5 $OUT/bpmc_$C.err; exit 1; }
+      python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_$C.json 2> $OUT/bpmc_$C.err || { echo "bench pmc $C failed"; tail -5 $OUT/bpmc_$C.err; exit 1; }
   timeout -s KILL 300 rocprofv3 --pmc $C --output-format csv -d $OUT/lpmc_$C -o run -- \
       python3 $R/tools/layer_bench.py --reps 2 --seq-out $OUT/seq.json > $OUT/lpmc_$C.log 2>&1 || { echo "layer pmc $C failed"; tail -5 $OUT/lpmc_$C.log; exit 1; }
 done

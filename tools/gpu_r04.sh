@@ -10,7 +10,7 @@ if [ "$2" != "skip-tests" ]; then
   rc=$?; tail -3 $OUT/pytest_gpu.log; [ $rc -ne 0 ] && { grep -E "Error|assert" $OUT/pytest_gpu.log | tail -20; exit $rc; }
 fi
 bash $R/tools/policy_sweep.sh ${1:-r04}/sweep || exit 1
-timeout -k 10 300 python3 $R/bench.py --scale m --imgsz 1280 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c4_m1280.json 2> $OUT/c4.err || { tail -5 $OUT/c4.err; exit 1; }
+timeout -k 10 300 python3 $R/bench.py --full --scale m --imgsz 1280 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c4_m1280.json 2> $OUT/c4.err || { tail -5 $OUT/c4.err; exit 1; }
 echo "C4: $(tail -1 $OUT/c4.err)"
 timeout -k 10 300 python3 $R/tools/infer_bench.py --batches 1 8 128 --no-cpu-baseline > $OUT/c5_infer.json 2> $OUT/c5.err || { tail -5 $OUT/c5.err; exit 1; }
 cat $OUT/c5_infer.json | cut -c1-300

@@ -9,7 +9,7 @@ tail -2 $OUT/capture3.log
 timeout -k 10 200 python3 -u -m pytest $R/tests/test_gpu_determinism.py -x -q --timeout 120 --timeout-method thread > $OUT/det.log 2>&1 || { echo "determinism failed"; tail -30 $OUT/det.log; exit 1; }
 tail -1 $OUT/det.log
 run_bench() {   # $1 tag; YM_GRAPH / YM_STREAMS set by the caller
-  timeout -k 10 300 python3 $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline > $OUT/bench_$1.json 2> $OUT/bench_$1.err || { echo "bench $1 failed"; tail -5 $OUT/bench_$1.err; return 1; }
+  timeout -k 10 300 python3 $R/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > $OUT/bench_$1.json 2> $OUT/bench_$1.err || { echo "bench $1 failed"; tail -5 $OUT/bench_$1.err; return 1; }
   python3 -c "import json; d=json.load(open('$OUT/bench_$1.json')); print('$1', d['value'], d['ms_per_step'], d['host_enqueue_ms_per_step'])"
 }
 YM_GRAPH=0 run_bench eager && YM_GRAPH=1 YM_STREAMS=3 run_bench graph3 && YM_GRAPH=1 YM_STREAMS=2 run_bench graph2 && YM_GRAPH=0 run_bench eager_b

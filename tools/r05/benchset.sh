@@ -12,7 +12,7 @@ for i in "${!CFGS[@]}"; do
   c="${CFGS[$i]}"; [ "$c" = "-" ] && c=""
   lib=""; envs=()
   for kv in $c; do case "$kv" in ym_*) lib="$lib $kv";; *) envs+=("$kv");; esac; done
-  env "${envs[@]}" YM_LIB_SET="$lib" timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/c${i}_r$rep.json 2> $O/c${i}_r$rep.err || { tail -5 $O/c${i}_r$rep.err; exit 1; }
+  env "${envs[@]}" YM_LIB_SET="$lib" timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/c${i}_r$rep.json 2> $O/c${i}_r$rep.err || { tail -5 $O/c${i}_r$rep.err; exit 1; }
   echo "rep $rep [${CFGS[$i]}] $(python -c "
 import json
 d = json.loads(open('$O/c${i}_r$rep.json').read().strip().splitlines()[-1]); print(d['value'], 'img/s', d['ms_per_step'], 'ms')")"

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
 tail -1 $O/test.log
 for rep in 1 2 3; do
   for mode in -1 2; do
-    YM_LIB_SET="ym_bn_set_bwd_fold=$mode" timeout -k 10 400 python -u bench.py --no-cpu-baseline --steps 30 > $O/b_${mode}_$rep.json 2> $O/b_${mode}_$rep.err || { tail -5 $O/b_${mode}_$rep.err; exit 1; }
+    YM_LIB_SET="ym_bn_set_bwd_fold=$mode" timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --steps 30 > $O/b_${mode}_$rep.json 2> $O/b_${mode}_$rep.err || { tail -5 $O/b_${mode}_$rep.err; exit 1; }
     echo "rep $rep mode $mode $(python -c "import json; d=json.load(open('$O/b_${mode}_$rep.json')); print(d['value'], d['ms_per_step'], 'bn', d['roofline_families']['bn']['ms_per_step'], d['roofline_families']['bn']['launch_groups'])")"
   done
 done

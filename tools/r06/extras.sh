@@ -4,7 +4,7 @@ set -o pipefail
 O=gpurun_out/r06_extras
 rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 300 python -u bench.py --scale m --imgsz 1280 --batch 16 --steps 20 --warmup 3 --no-cpu-baseline > $O/c4_m1280.json 2> $O/c4.err || { tail -5 $O/c4.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --scale m --imgsz 1280 --batch 16 --steps 20 --warmup 3 --no-cpu-baseline > $O/c4_m1280.json 2> $O/c4.err || { tail -5 $O/c4.err; exit 1; }
 tail -c 300 $O/c4_m1280.json; echo
 for rep in 1 2; do
   timeout -k 10 300 python -u tools/infer_bench.py --batches 1 8 128 --reps 200 --no-cpu-baseline > $O/c5_r$rep.json 2> $O/c5_r$rep.err || { tail -5 $O/c5_r$rep.err; exit 2; }

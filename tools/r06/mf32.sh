@@ -10,5 +10,5 @@ rc=$?; tail -3 $O/pytest.log; grep -E "FAILED|Error" $O/pytest.log | head -20
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 500 python -u tools/pipe_ab.py ym_conv_set_pipe_mfma --setter2 ym_conv_set_pipe_order --only 6 10 11 52 73 74 78 48 47 71 8 53 --variants 0:0 0:1 1:0 2:0 2:1 --rounds 3 > $O/ab.txt 2>&1 || { tail -20 $O/ab.txt; exit 2; }
 cat $O/ab.txt
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
 tail -c 400 $O/bench.json

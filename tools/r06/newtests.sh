@@ -8,5 +8,5 @@ timeout -k 10 1100 python -u -m pytest tests/test_gpu_c5_eval.py tests/test_gpu_
 rc=$?
 grep -E "PASS|FAIL|Error|worst|level|kept|assert|passed|failed" $O/pytest.log | head -60
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 tail -c 600 $O/bench.json

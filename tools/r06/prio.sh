@@ -9,6 +9,6 @@ YM_STREAM_PRIO=1 timeout -k 10 600 python -u -m pytest tests/test_gpu_determinis
 rc=$?; tail -3 $O/pytest.log; grep -E "FAILED|Error" $O/pytest.log | head -20
 [ $rc -eq 0 ] || exit $rc
 for rep in 1 2 3; do for f in 1 0; do
-  YM_STREAM_PRIO=$f timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 100 > $O/bench_p${f}_r$rep.json 2> $O/bench_p${f}_r$rep.err || { tail -5 $O/bench_p${f}_r$rep.err; exit 3; }
+  YM_STREAM_PRIO=$f timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 100 > $O/bench_p${f}_r$rep.json 2> $O/bench_p${f}_r$rep.err || { tail -5 $O/bench_p${f}_r$rep.err; exit 3; }
   python3 -c "import json;d=json.loads(open('$O/bench_p${f}_r$rep.json').read().strip().splitlines()[-1]);print('prio=$f rep=$rep', d['value'], d['ms_per_step'])"
 done; done
