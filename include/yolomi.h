@@ -428,6 +428,40 @@ int ym_dfl_bwd(const float* x, int64_t B, int64_t A, int c1, const float* w, con
  * (datasets/crater_dataset_cuda.py:182-184, 253). */
 int ym_resize_linear_u8(const uint8_t* src, const int64_t* meta, int batch, int size, float* out, void* stream);
 
+/* Training augmentation in the same launch shape: every output image is up to four tiles (mosaic quadrants)
+ * of images of THIS batch over a fill value, each sampled bilinearly through its own 2x3 map, then a value
+ * gain, then /255 -> fp32.  The reference constructs its dataset with augment=True (train_yolo11_cuda.py:491)
+ * and never reads the flag; this is what the flag stands for.  All arithmetic is integer fixed point
+ * (include/yolomi_augment.h holds the per-pixel function, shared by the kernel and host programs):
+ *   coordinates  int64 with YM_AUG_FB = 24 fraction bits: pos = m[0] * x + m[1] * y + m[2] (x, y the output
+ *                pixel index; |m[0]|, |m[1]| < 2^40 and |m[2]| < 2^56 keep the sum inside int64)
+ *   tile choice  canvas position through `c`; quadrant = (cx >= xc) + 2 * (cy >= yc); the tile of that slot is
+ *                sampled where x0 <= cx < x1 and y0 <= cy < y1 and its src is in [0, batch), else `fill`
+ *   sampling     position rounded to 11 fraction bits, taps clamped to the source image's edge, combined as in
+ *                ym_resize_linear_u8
+ *   gain         min((v * gain) >> 16, 255) on the 8-bit value (fill included), gain in Q16
+ * An entry with YM_AUG_STRETCH set ignores the maps and is ym_resize_linear_u8 of tile[0].src bit for bit
+ * (then the gain). */
+#define YM_AUG_FB 24
+#define YM_AUG_STRETCH 1
+typedef struct ym_aug_tile {
+    int64_t m[6];              /* output pixel -> source pixel position: u = m0 x + m1 y + m2, v = m3 x + m4 y + m5 */
+    int64_t x0, y0, x1, y1;    /* the part of the canvas the tile owns (canvas coordinates, half open) */
+    int32_t src;               /* index of the source image in this batch; < 0: empty slot */
+    int32_t reserved;
+} ym_aug_tile;
+typedef struct ym_aug_entry {
+    ym_aug_tile tile[4];       /* slot = quadrant relative to (xc, yc); a plain image sits in slot 0 */
+    int64_t c[6];              /* output pixel -> canvas position */
+    int64_t xc, yc;            /* mosaic centre in canvas coordinates (INT64_MAX: every pixel in slot 0) */
+    int32_t gain;              /* Q16: 65536 is 1.0 */
+    int32_t fill;              /* 0..255 */
+    int32_t flags;             /* YM_AUG_STRETCH */
+    int32_t reserved;
+} ym_aug_entry;
+int ym_augment_u8(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev, int batch, int size,
+                  float* out, void* stream);
+
 /* ------------------------------------------------------------------ optimizer tail
  * clip_grad_norm_(params, max_norm) + AdamW.step() over every parameter (train_yolo11_cuda.py:58-62,
  * 440-451).  The parameters form one flat index space: entry e covers elements [offset, offset + n)

@@ -14,23 +14,23 @@
 //   out = ((b0 * (h(sy) >> 4)) >> 16) + ((b1 * (h(sy1) >> 4)) >> 16) + 2) >> 2, clamped to 0..255
 //        (the vertical rounding of OpenCV's SIMD path, which covers every column when S % 16 == 0)
 // Images already S x S are copied unchanged (the reference skips the resize there, :183).
+// The coefficient rule (ym_aug_lin_coeff) lives in include/yolomi_augment.h, shared with the augmentation.
+//
+// Training augmentation (ym_augment_u8): the same launch shape with a per-image table entry (ym_aug_entry,
+// include/yolomi.h) of up to four mosaic tiles, each with its own 2x3 output-pixel -> source-position map, a
+// fill byte and a value gain.  The arithmetic is all integer and lives in include/yolomi_augment.h
+// (ym_aug_sample; the formats are stated in that file's header): int64 positions with 24 fraction bits, rounded
+// to 11-bit weights, taps clamped to the source image, the interpolation above, gain in Q16.  The kernel below is
+// a loop around that function's pieces: blockIdx.y walks images, so the table entry is block-uniform (scalar loads);
+// each thread produces four consecutive pixels of the flat S * S image and writes them with one 16-byte store
+// (lanes of a wave cover 1 KiB of contiguous output); blockIdx.x grid-strides over the image.
 #include <algorithm>
 
 #include "common.h"
+#include "yolomi_augment.h"
 
 namespace ym {
 namespace {
-
-__device__ __forceinline__ void lin_coeff(int d, double scale, int n, int& s, int& a0, int& a1) {
-    float f = float((d + 0.5) * scale - 0.5);
-    int si = int(floorf(f));
-    f -= float(si);
-    if (si < 0) { f = 0.f; si = 0; }
-    if (si >= n - 1) { f = 0.f; si = n - 1; }
-    s = si;
-    a0 = __float2int_rn((1.f - f) * 2048.f);
-    a1 = __float2int_rn(f * 2048.f);
-}
 
 // meta[b] = {byte offset of image b in src, h0, w0}; out (B, 1, S, S) fp32
 __global__ void resize_linear_u8_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta, int S,
@@ -47,8 +47,8 @@ __global__ void resize_linear_u8_kernel(const uint8_t* __restrict__ src, const i
             v = im[p];
         } else {
             int sx, a0, a1, sy, b0, b1;
-            lin_coeff(dx, double(w0) / S, w0, sx, a0, a1);
-            lin_coeff(dy, double(h0) / S, h0, sy, b0, b1);
+            ym_aug_lin_coeff(dx, double(w0) / S, w0, sx, a0, a1);
+            ym_aug_lin_coeff(dy, double(h0) / S, h0, sy, b0, b1);
             const int sx1 = min(sx + 1, w0 - 1), sy1 = min(sy + 1, h0 - 1);
             const uint8_t* r0 = im + int64_t(sy) * w0;
             const uint8_t* r1 = im + int64_t(sy1) * w0;
@@ -58,6 +58,52 @@ __global__ void resize_linear_u8_kernel(const uint8_t* __restrict__ src, const i
             v = min(max(v, 0), 255);
         }
         out[i] = float(v) / 255.0f;
+    }
+}
+
+// ym_aug_sample for a block-uniform entry `e`.  A wave covers 256 consecutive pixels, so nearly always one slot:
+// then the tile is addressed by the slot of the first lane, a scalar, and its maps, rectangle and source meta
+// come through scalar loads instead of ~25 per-lane loads of the same words.
+__device__ __forceinline__ int augment_pixel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                             int batch, int S, const ym_aug_entry* __restrict__ e, int x, int y) {
+    if (e->flags & YM_AUG_STRETCH) return ym_aug_gain(e->gain, ym_aug_stretch_value(src, meta, batch, S, e, x, y));
+    int64_t cx, cy;
+    const int slot = ym_aug_slot(e, x, y, cx, cy);
+    const int first = __builtin_amdgcn_readfirstlane(slot);
+    int v;
+    if (__all(slot == first))
+        v = ym_aug_tile_value(src, meta, batch, e->fill, &e->tile[first], cx, cy, x, y);
+    else
+        v = ym_aug_tile_value(src, meta, batch, e->fill, &e->tile[slot], cx, cy, x, y);
+    return ym_aug_gain(e->gain, v);
+}
+
+// out (B, 1, S, S) fp32; `vec`: S * S % 4 == 0 and out 16-byte aligned, so every group of four is one aligned store
+__global__ void augment_u8_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                  const ym_aug_entry* __restrict__ table, int batch, int S, int vec,
+                                  float* __restrict__ out) {
+    const int SS = S * S;
+    const int groups = (SS + 3) >> 2;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const ym_aug_entry* e = table + b;
+        float* o = out + int64_t(b) * SS;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / S, x = p - y * S;
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                v[k] = p + k < SS ? float(augment_pixel(src, meta, batch, S, e, x, y)) / 255.0f : 0.f;
+                if (++x == S) { x = 0; ++y; }
+            }
+            if (vec) {
+                *reinterpret_cast<float4*>(o + p) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (p + k < SS) o[p + k] = v[k];
+            }
+        }
     }
 }
 
@@ -75,5 +121,20 @@ extern "C" int ym_resize_linear_u8(const uint8_t* src, const int64_t* meta, int 
     hipLaunchKernelGGL(resize_linear_u8_kernel, dim3(unsigned(blocks)), dim3(256), 0, as_stream(stream), src, meta, size,
                        total, out);
     YM_LAUNCH_CHECK("ym_resize_linear_u8");
+    return YM_OK;
+}
+
+extern "C" int ym_augment_u8(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev, int batch,
+                             int size, float* out, void* stream) {
+    YM_CHECK_ARG(src && meta && table_dev && out && batch >= 0 && size > 0 && size <= 32768,
+                 "ym_augment_u8: bad arguments");
+    if (batch == 0) return YM_OK;
+    const int64_t ss = int64_t(size) * size;
+    const int64_t groups = (ss + 3) / 4;
+    const int vec = ss % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const int64_t bx = std::min<int64_t>((groups + 255) / 256, 256);      // per image; larger images grid-stride
+    hipLaunchKernelGGL(augment_u8_kernel, dim3(unsigned(bx), unsigned(std::min(batch, 65535))), dim3(256), 0,
+                       as_stream(stream), src, meta, table_dev, batch, size, vec, out);
+    YM_LAUNCH_CHECK("ym_augment_u8");
     return YM_OK;
 }

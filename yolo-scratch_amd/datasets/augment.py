@@ -1,0 +1,280 @@
+"""Training augmentation on the GPU: mosaic, random affine, flips and a value gain in one launch.
+
+The reference trainer builds its dataset with augment=True (train_yolo11_cuda.py:491) and never reads the flag
+(crater_dataset_cuda.py:50).  Here the flag's meaning is supplied in the Ultralytics v8 style: `BatchAugment` draws
+every image's parameters on the host, composes flip, affine, mosaic placement and the loader's S-stretch into one
+2x3 map per tile, rounds the maps once to fixed point (include/yolomi.h: ym_aug_entry) and one ym_augment_u8 launch
+samples the packed uint8 batch that `collate_fn_cuda` produced straight into the fp32 (B, 1, S, S) batch.  No S x S
+intermediate exists; a mosaic's three extra tiles are other images of the same batch, already in HBM.  The boxes
+(a few dozen rows) are transformed on the host, which therefore still knows max_gt.
+
+Geometry (Ultralytics Mosaic + RandomPerspective without the perspective term), in pixel-index coordinates:
+  canvas     without mosaic the S x S stretch of the image; with mosaic 2S x 2S, centre (xc, yc) integer uniform in
+             [S/2, 3S/2)^2, four S x S stretched tiles touching the centre with one corner, cropped by the canvas
+  affine     A = T * Shear * R(angle, scale) * C: C moves the canvas centre to the origin, T moves it to
+             uniform(0.5 - translate, 0.5 + translate) * S; the output is the S x S window at the origin
+  flips      on the output (pixel index S - 1 - x; boxes 1 - x on the normalised coordinate)
+An image whose geometry is the identity is flagged YM_AUG_STRETCH and equals the validation path's resize bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+import math
+
+import numpy as np
+import torch
+
+from yolomi._lib import AugEntry, AugTile
+
+FB = 24                        # YM_AUG_FB
+STRETCH = 1                    # YM_AUG_STRETCH
+_I64_MAX = (1 << 63) - 1
+
+
+@dataclasses.dataclass
+class AugmentHyp:
+    """Hyperparameters, named as in Ultralytics' v8 trainer (`gain` is their hsv_v: the images are single-plane)."""
+    mosaic: float = 1.0
+    degrees: float = 0.0
+    translate: float = 0.1
+    scale: float = 0.5
+    shear: float = 0.0
+    fliplr: float = 0.5
+    flipud: float = 0.0
+    gain: float = 0.4
+    fill: int = 114
+
+    def is_off(self) -> bool:
+        return not any((self.mosaic, self.degrees, self.translate, self.scale, self.shear, self.fliplr, self.flipud,
+                        self.gain))
+
+
+def _fix(v) -> int:
+    """fp64 -> fixed point with FB fraction bits, rounded once."""
+    return int(np.rint(np.float64(v) * np.float64(1 << FB)))
+
+
+def translation(tx, ty):
+    return np.array([[1.0, 0.0, tx], [0.0, 1.0, ty], [0.0, 0.0, 1.0]])
+
+
+def stretch_map(h0: int, w0: int, S: int):
+    """Stretched-tile pixel index -> source pixel position: u = (j + 0.5) * w0 / S - 0.5 (the loader's resize)."""
+    return np.array([[w0 / S, 0.0, 0.5 * w0 / S - 0.5], [0.0, h0 / S, 0.5 * h0 / S - 0.5], [0.0, 0.0, 1.0]])
+
+
+def make_tile(src: int, m, rect) -> AugTile:
+    """`m`: 2x3 (or 3x3) fp64 output pixel -> source position; `rect`: (x0, y0, x1, y1) canvas, half open."""
+    t = AugTile()
+    m = np.asarray(m, np.float64)
+    for i in range(6):
+        t.m[i] = _fix(m[i // 3, i % 3])
+    t.x0, t.y0, t.x1, t.y1 = (_fix(v) for v in rect)
+    t.src = int(src)
+    return t
+
+
+def make_entry(tiles, c, centre=None, gain=1.0, fill=114, stretch=False) -> AugEntry:
+    """`tiles`: up to four AugTile or None by slot (slot = (cx >= xc) + 2 * (cy >= yc)); `c`: fp64 output pixel ->
+    canvas; `centre`: (xc, yc) canvas pixel index of the first pixel of the right / lower tiles, or None."""
+    e = AugEntry()
+    for k in range(4):
+        t = tiles[k] if k < len(tiles) else None
+        if t is None:
+            e.tile[k].src = -1
+        else:
+            e.tile[k] = t
+    c = np.asarray(c, np.float64)
+    for i in range(6):
+        e.c[i] = _fix(c[i // 3, i % 3])
+    if centre is None:
+        e.xc = e.yc = _I64_MAX
+    else:
+        e.xc, e.yc = _fix(centre[0] - 0.5), _fix(centre[1] - 0.5)
+    e.gain = int(np.rint(np.float64(gain) * 65536.0))
+    e.fill = int(fill)
+    e.flags = STRETCH if stretch else 0
+    return e
+
+
+def plain_entry(src: int, h0: int, w0: int, S: int, inv=None, gain=1.0, fill=114) -> AugEntry:
+    """One stretched image under `inv` (3x3 fp64, output pixel -> canvas pixel; None: identity, flagged)."""
+    if inv is None:
+        return make_entry([make_tile(src, stretch_map(h0, w0, S), (-0.5, -0.5, S - 0.5, S - 0.5))], np.eye(3), None,
+                          gain, fill, stretch=True)
+    tile = make_tile(src, stretch_map(h0, w0, S) @ inv, (-0.5, -0.5, S - 0.5, S - 0.5))
+    return make_entry([tile], inv, None, gain, fill)
+
+
+def mosaic_origins(xc: int, yc: int, S: int):
+    """Canvas pixel index of each slot's tile origin: the tiles touch (xc, yc) with one corner."""
+    return [(xc - S, yc - S), (xc, yc - S), (xc - S, yc), (xc, yc)]
+
+
+def mosaic_entry(srcs, sizes, xc: int, yc: int, S: int, inv, gain=1.0, fill=114) -> AugEntry:
+    """Four stretched tiles (`srcs` batch indices, `sizes` their (h0, w0)) on the 2S canvas around (xc, yc)."""
+    tiles = []
+    for (ox, oy), b, (h0, w0) in zip(mosaic_origins(xc, yc, S), srcs, sizes):
+        rect = (max(ox, 0) - 0.5, max(oy, 0) - 0.5, min(ox + S, 2 * S) - 0.5, min(oy + S, 2 * S) - 0.5)
+        tiles.append(make_tile(b, stretch_map(h0, w0, S) @ translation(-ox, -oy) @ inv, rect))
+    return make_entry(tiles, inv, (xc, yc), gain, fill)
+
+
+def affine_matrix(S: int, canvas: int, angle=0.0, scale=1.0, shear_x=0.0, shear_y=0.0, tx=0.5, ty=0.5):
+    """A = T * Shear * R * C (3x3 fp64, canvas pixel -> output pixel); angles in degrees, tx / ty fractions of S."""
+    C = translation(-canvas / 2, -canvas / 2)
+    a = math.radians(angle)
+    R = np.array([[scale * math.cos(a), scale * math.sin(a), 0.0], [-scale * math.sin(a), scale * math.cos(a), 0.0],
+                  [0.0, 0.0, 1.0]])
+    Sh = np.array([[1.0, math.tan(math.radians(shear_x)), 0.0], [math.tan(math.radians(shear_y)), 1.0, 0.0],
+                   [0.0, 0.0, 1.0]])
+    return translation(tx * S, ty * S) @ Sh @ R @ C
+
+
+def flip_matrix(S: int, lr: bool, ud: bool):
+    """Output pixel index flips (3x3 fp64)."""
+    F = np.eye(3)
+    if lr:
+        F[0, 0], F[0, 2] = -1.0, S - 1.0
+    if ud:
+        F[1, 1], F[1, 2] = -1.0, S - 1.0
+    return F
+
+
+def box_candidates(pre, post, wh_thr=2.0, ar_thr=100.0, area_thr=0.1, eps=1e-16):
+    """Ultralytics' filter on pixel xyxy rows: `pre` before and `post` after clipping to the image."""
+    w1, h1 = pre[:, 2] - pre[:, 0], pre[:, 3] - pre[:, 1]
+    w2, h2 = post[:, 2] - post[:, 0], post[:, 3] - post[:, 1]
+    ar = np.maximum(w2 / (h2 + eps), h2 / (w2 + eps))
+    return (w2 > wh_thr) & (h2 > wh_thr) & (w2 * h2 / (w1 * h1 + eps) >= area_thr) & (ar < ar_thr)
+
+
+def transform_boxes(xyxy, A, S: int, lr: bool, ud: bool):
+    """Canvas pixel xyxy (n, 4) fp64 -> (normalised xyxy of the survivors, keep mask): the four corners through A,
+    their axis-aligned hull, clipped to [0, S], filtered, normalised, flipped."""
+    n = len(xyxy)
+    if n == 0:
+        return np.zeros((0, 4)), np.zeros((0,), bool)
+    pts = np.ones((n * 4, 3))
+    pts[:, :2] = xyxy[:, [0, 1, 2, 3, 0, 3, 2, 1]].reshape(n * 4, 2)
+    pts = (pts @ A.T)[:, :2].reshape(n, 4, 2)
+    pre = np.concatenate([pts.min(1), pts.max(1)], 1)
+    post = np.clip(pre, 0.0, float(S))
+    keep = box_candidates(pre, post)
+    out = post[keep] / float(S)
+    if lr:
+        out[:, [0, 2]] = 1.0 - out[:, [2, 0]]
+    if ud:
+        out[:, [1, 3]] = 1.0 - out[:, [3, 1]]
+    return out, keep
+
+
+def step_seed(seed: int, rank: int, epoch: int, step: int) -> int:
+    """One 63-bit generator seed from the four counters (any one changing changes it)."""
+    ss = np.random.SeedSequence([int(seed) & 0xFFFFFFFF, int(rank), int(epoch), int(step)])
+    return int(ss.generate_state(1, np.uint64)[0]) & _I64_MAX
+
+
+def augment_batch(img_u8: torch.Tensor, meta: torch.Tensor, table: torch.Tensor, img_size: int) -> torch.Tensor:
+    """GPU: packed uint8 images + device table of ym_aug_entry (uint8 bytes) -> (B, 1, S, S) fp32 (ym_augment_u8)."""
+    from yolomi._lib import call, require_device, stream_ptr
+    require_device(img_u8, meta, table)
+    B = meta.shape[0]
+    assert table.dtype == torch.uint8 and table.numel() == B * ctypes.sizeof(AugEntry)
+    out = torch.empty(B, 1, img_size, img_size, dtype=torch.float32, device=img_u8.device)
+    call("ym_augment_u8", img_u8.data_ptr(), meta.contiguous().data_ptr(), table.data_ptr(), B, img_size,
+         out.data_ptr(), stream_ptr(img_u8.device))
+    return out
+
+
+def table_bytes(entries) -> torch.Tensor:
+    """ctypes array of AugEntry -> host uint8 tensor (a copy)."""
+    return torch.from_numpy(np.frombuffer(bytes(entries), dtype=np.uint8).copy())
+
+
+class BatchAugment:
+    """Draws a batch's augmentation on the host and applies it on the device (see the module doc).
+
+    aug(batch, device, epoch, step) takes a collated host batch and returns the dict `prepare_batch` returns (img,
+    batch_idx, cls, bboxes, max_gt).  The parameters come from a torch.Generator seeded from (seed, rank, epoch,
+    step): a run is reproducible, ranks differ, and resuming needs no saved state.  `no_mosaic_from`: epochs (the
+    number handed to the call) from this one on draw no mosaic."""
+
+    def __init__(self, hyp: AugmentHyp | None = None, seed: int = 0, rank: int = 0, no_mosaic_from: int | None = None):
+        self.hyp = hyp or AugmentHyp()
+        self.seed, self.rank, self.no_mosaic_from = int(seed), int(rank), no_mosaic_from
+
+    def draw(self, B: int, epoch: int, step: int) -> dict:
+        """Per-image parameters (numpy arrays of length B)."""
+        h = self.hyp
+        g = torch.Generator().manual_seed(step_seed(self.seed, self.rank, epoch, step))
+        u = torch.rand(B, 11, generator=g, dtype=torch.float64).numpy()
+        partners = torch.randint(0, max(B, 1), (B, 3), generator=g).numpy()
+        mosaic_on = self.no_mosaic_from is None or epoch < self.no_mosaic_from
+        sym = lambda col, r: (2.0 * u[:, col] - 1.0) * r        # noqa: E731  uniform(-r, r)
+        return {"mosaic": (u[:, 0] < h.mosaic) & mosaic_on, "cx": u[:, 1], "cy": u[:, 2], "partners": partners,
+                "angle": sym(3, h.degrees), "scale": 1.0 + sym(4, h.scale), "shear_x": sym(5, h.shear),
+                "shear_y": sym(6, h.shear), "tx": 0.5 + sym(7, h.translate), "ty": 0.5 + sym(8, h.translate),
+                "fliplr": u[:, 9] < h.fliplr, "flipud": u[:, 10] < h.flipud,
+                "gain": 1.0 + (2.0 * torch.rand(B, generator=g, dtype=torch.float64).numpy() - 1.0) * h.gain}
+
+    def plan(self, batch: dict, epoch: int, step: int):
+        """Host side of one batch -> (ctypes table of AugEntry, batch_idx, cls, bboxes, max_gt)."""
+        from .crater import max_gt_count
+        meta = batch["img_meta"].numpy()
+        S, B = int(batch["img_size"]), int(meta.shape[0])
+        p = self.draw(B, epoch, step)
+        bidx = batch["batch_idx"].numpy().reshape(-1)
+        boxes = batch["bboxes"].numpy().astype(np.float64).reshape(-1, 4)
+        cls = batch["cls"].numpy()
+        rows_of = [np.nonzero(bidx == i)[0] for i in range(B)]
+        table = (AugEntry * max(B, 1))()
+        o_idx, o_cls, o_box = [], [], []
+        for i in range(B):
+            lr, ud, gain = bool(p["fliplr"][i]), bool(p["flipud"][i]), float(p["gain"][i])
+            mosaic = bool(p["mosaic"][i])
+            A = affine_matrix(S, 2 * S if mosaic else S, p["angle"][i], p["scale"][i], p["shear_x"][i], p["shear_y"][i],
+                              p["tx"][i], p["ty"][i])
+            if not mosaic and not lr and not ud and np.array_equal(A, np.eye(3)):
+                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, None, gain, self.hyp.fill)
+                rows = rows_of[i]
+                o_idx.append(np.full(len(rows), i)), o_cls.append(cls[rows]), o_box.append(boxes[rows])
+                continue
+            inv = np.linalg.inv(A) @ flip_matrix(S, lr, ud)          # output pixel -> canvas pixel
+            if mosaic:
+                xc, yc = (int(S / 2 + c * S) for c in (p["cx"][i], p["cy"][i]))
+                srcs = [i, *(int(b) for b in p["partners"][i])]
+                table[i] = mosaic_entry(srcs, [(int(meta[b, 1]), int(meta[b, 2])) for b in srcs], xc, yc, S, inv, gain,
+                                        self.hyp.fill)
+                parts = []
+                for (ox, oy), b in zip(mosaic_origins(xc, yc, S), srcs):
+                    parts.append(np.clip(boxes[rows_of[b]] * S + np.array([ox, oy, ox, oy], np.float64), 0, 2 * S))
+                canvas_boxes = np.concatenate(parts)
+                rows = np.concatenate([rows_of[b] for b in srcs])
+            else:
+                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, inv, gain, self.hyp.fill)
+                rows = rows_of[i]
+                canvas_boxes = boxes[rows] * S
+            out, keep = transform_boxes(canvas_boxes, A, S, lr, ud)
+            o_idx.append(np.full(len(out), i)), o_cls.append(cls[rows][keep]), o_box.append(out)
+        if B == 0 or not sum(len(x) for x in o_idx):
+            bi, cl, bb = (torch.zeros((0,), dtype=torch.long), torch.zeros((0, 1), dtype=batch["cls"].dtype),
+                          torch.zeros((0, 4), dtype=torch.float32))
+        else:
+            bi = torch.from_numpy(np.concatenate(o_idx)).long()
+            cl = torch.from_numpy(np.concatenate(o_cls)).to(batch["cls"].dtype).reshape(-1, 1)
+            bb = torch.from_numpy(np.concatenate(o_box)).float().clamp_(0.0, 1.0)
+        return table, bi, cl, bb, max_gt_count(bi)
+
+    def __call__(self, batch: dict, device, epoch: int, step: int) -> dict:
+        from .crater import prepare_batch
+        if "img_u8" not in batch or self.hyp.is_off() or batch["img_meta"].shape[0] == 0:
+            return prepare_batch(batch, device)              # synthetic batches carry no raw images
+        table, bi, cl, bb, max_gt = self.plan(batch, epoch, step)
+        tb = table_bytes(table)
+        if torch.device(device).type == "cuda":
+            tb = tb.pin_memory()
+        mv = lambda t: t.to(device, non_blocking=True)          # noqa: E731
+        img = augment_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), mv(tb), int(batch["img_size"]))
+        return {"max_gt": max_gt, "img": img, "batch_idx": mv(bi), "cls": mv(cl), "bboxes": mv(bb)}

@@ -43,14 +43,19 @@ def _tqdm(it, **kw):
         return it
 
 
-def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epochs, dp=None):
-    """One epoch (reference :31-98).  `dp` is an optional yolomi.dist.GradSync."""
+def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epochs, dp=None, augment=None):
+    """One epoch (reference :31-98).  `dp` is an optional yolomi.dist.GradSync; `augment` an optional
+    datasets.BatchAugment, applied in place of prepare_batch (the train and val subsets share one dataset
+    object, so the switch lives in the step: validate never augments)."""
     model.train()
     pbar = _tqdm(dataloader, desc=f"Epoch {epoch}/{epochs}")
     sums = torch.zeros(4, device=device)
     n = 0
     for batch_idx, batch in enumerate(pbar):
-        batch = prepare_batch(batch, device)        # H2D (+ GPU resize of raw images)
+        if augment is not None:
+            batch = augment(batch, device, epoch, batch_idx)      # H2D + mosaic / affine / flip / gain in one launch
+        else:
+            batch = prepare_batch(batch, device)        # H2D (+ GPU resize of raw images)
         optimizer.zero_grad(set_to_none=True)
         preds = model(batch["img"])
         loss, loss_items = criterion(preds, batch)
@@ -266,6 +271,18 @@ def main():
     ap.add_argument("--max-val-batches", type=int, default=None)
     ap.add_argument("--val-conf", type=float, default=0.25)
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic batches (no dataset needed)")
+    ap.add_argument("--augment", action="store_true", help="GPU training augmentation (datasets/augment.py)")
+    ap.add_argument("--mosaic", type=float, default=1.0, help="probability of a 4-tile mosaic")
+    ap.add_argument("--degrees", type=float, default=0.0, help="rotation range (+/- degrees)")
+    ap.add_argument("--translate", type=float, default=0.1, help="translation range (+/- fraction of the image)")
+    ap.add_argument("--aug-scale", type=float, default=0.5, help="scale range (+/- gain); Ultralytics' `scale`, "
+                    "renamed because --scale selects the model size")
+    ap.add_argument("--shear", type=float, default=0.0, help="shear range (+/- degrees)")
+    ap.add_argument("--fliplr", type=float, default=0.5, help="probability of a left-right flip")
+    ap.add_argument("--flipud", type=float, default=0.0, help="probability of an up-down flip")
+    ap.add_argument("--gain", type=float, default=0.4, help="value gain range (+/- fraction; Ultralytics' hsv_v)")
+    ap.add_argument("--close-mosaic", type=int, default=10, help="no mosaic in the last N epochs")
+    ap.add_argument("--aug-seed", type=int, default=0)
     args = ap.parse_args()
 
     from yolomi import dist as ydist
@@ -315,12 +332,22 @@ def main():
     if dp:
         dp.broadcast_state()
 
+    augment = None
+    if args.augment:
+        from datasets import AugmentHyp, BatchAugment
+        hyp = AugmentHyp(mosaic=args.mosaic, degrees=args.degrees, translate=args.translate, scale=args.aug_scale,
+                         shear=args.shear, fliplr=args.fliplr, flipud=args.flipud, gain=args.gain)
+        # train_one_epoch counts epochs from 1: the last `close_mosaic` of them draw no mosaic
+        augment = BatchAugment(hyp, seed=args.aug_seed, rank=dp_ctx.rank if dp_ctx else 0,
+                               no_mosaic_from=args.epochs - args.close_mosaic + 1)
+
     for epoch in range(start_epoch, args.epochs):
         lr = cosine_lr_schedule(optimizer, epoch, args.epochs, lr_min=args.lr * 0.01, lr_max=args.lr, warmup_epochs=3)
         criterion.epoch = epoch
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
-        tm = train_one_epoch(model, train_loader, optimizer, criterion, device, epoch + 1, args.epochs, dp)
+        tm = train_one_epoch(model, train_loader, optimizer, criterion, device, epoch + 1, args.epochs, dp,
+                             augment)
         if dp:
             dp.sync_buffers()          # rank 0's BN running statistics for validation and the checkpoint
         vm = validate(model, val_loader, criterion, device, conf_threshold=args.val_conf, iou_threshold=0.45,

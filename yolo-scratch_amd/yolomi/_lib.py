@@ -51,6 +51,17 @@ class BnFold(ctypes.Structure):
                 ("momentum", _c.c_float), ("eps", _c.c_float)]
 
 
+class AugTile(ctypes.Structure):
+    """ym_aug_tile (include/yolomi.h)."""
+    _fields_ = [("m", I64 * 6), ("x0", I64), ("y0", I64), ("x1", I64), ("y1", I64), ("src", I32), ("reserved", I32)]
+
+
+class AugEntry(ctypes.Structure):
+    """ym_aug_entry (include/yolomi.h)."""
+    _fields_ = [("tile", AugTile * 4), ("c", I64 * 6), ("xc", I64), ("yc", I64), ("gain", I32), ("fill", I32),
+                ("flags", I32), ("reserved", I32)]
+
+
 R = _c.c_int
 # name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (its YM_EXPERIMENTS block
 # excepted: the measurement library's)
@@ -150,6 +161,7 @@ SIGNATURES = {
     "ym_eval_ap": (R, [P, P, I64, I64, P, SZ, P, P]),
     "ym_iou_matrix": (R, [P, P, I64, I64, P, P]),
     "ym_resize_linear_u8": (R, [P, P, INT, INT, P, P]),
+    "ym_augment_u8": (R, [P, P, P, INT, INT, P, P]),
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),
