@@ -205,6 +205,8 @@ int ym_dw3x3_fwd(const uint16_t* x, int64_t x_bs, int64_t x_ld, int gsz, int gst
 int ym_dw3x3_fwd_eval(const uint16_t* x, int64_t x_bs, int64_t x_ld, int gsz, int gstride, int goff, const float* w,
                       const float* scale, const float* shift, int act, const uint16_t* res, int64_t r_bs, int64_t r_ld,
                       uint16_t* y, int64_t y_bs, int64_t y_ld, int n, int h, int wd, int c, void* stream);
+/* dx (bf16) goes to the SOURCE channels of the dx view (the same map as x), written, or added to what the view holds
+ * when accumulate; dw (fp32 [c][9]) is always ADDED to, whatever accumulate says — zero it for a plain gradient. */
 size_t ym_dw3x3_bwd_workspace_size(int c);
 int ym_dw3x3_bwd(const uint16_t* x, int64_t x_bs, int64_t x_ld, int gsz, int gstride, int goff, const float* w,
                  const uint16_t* dz, uint16_t* dx, int64_t dx_bs, int64_t dx_ld, float* dw, int n, int h, int wd,
@@ -218,7 +220,8 @@ int ym_prep_weights_fwd(const ym_wprep_entry* table_dev, int n_entries, int64_t 
 /* ------------------------------------------------------------------ BatchNorm2d (train) + SiLU
  * Replaces BatchNorm2d + the shared in-place SiLU of Conv (models/yolo11_modules.py:24-33;
  * eps 1e-3 / momentum 0.03 from yolo11_model.py:183-185).  z is the dense (m, c) conv output in
- * fp16 (written by ym_conv_fwd with out_f32 = 2); dz (bf16) may overwrite it in place.
+ * fp16 (written by ym_conv_fwd with out_f32 = 2); dz (bf16) may overwrite it in place: ym_bn_bwd_apply[_res]
+ * accept dz == z and give the same bits as into a fresh buffer.
  */
 /* scratch for the two-level partial reductions of ym_bn_finalize / ym_bn_bwd_finalize: fp64 rows
  * plus ticket counters.  Zero it once before first use (the library leaves the counters at zero
@@ -278,7 +281,9 @@ typedef struct ym_bn_eval_entry {
 int ym_bn_eval_coeff_batch(const ym_bn_eval_entry* table_dev, int n_entries, void* stream);
 int ym_bn_eval_coeff(int c, const float* gamma, const float* beta, const float* running_mean,
                      const float* running_var, float eps, float* scale, float* shift, void* stream);
-/* out_view = act(z*scale+shift) (+ res_view); act: 0 identity, 1 SiLU; hw = pixels per image */
+/* out_view = act(z*scale+shift) (+ res_view); act: 0 identity, 1 SiLU; hw = pixels per image.
+ * The fp16 store rounds to nearest even and clamps to +-65504 (never inf), as the fp16 stores of ym_dw3x3_fwd[_eval]
+ * and of ym_view_axpy with half = 1 do; out32 holds the value before that rounding and clamp. */
 int ym_bn_apply(const uint16_t* z, int64_t m, int c, int hw, const float* scale, const float* shift, int act,
                 const uint16_t* res, int64_t r_bs, int64_t r_ld, uint16_t* out, int64_t o_bs, int64_t o_ld,
                 float* out32, void* stream);   /* out32: optional fp32 dense copy (SPPF pool chain) */
@@ -345,7 +350,8 @@ int ym_view_to_f32(const uint16_t* x, int64_t bs, int64_t ld, float* y, int64_t 
 int ym_f32_to_view(const float* x, uint16_t* y, int64_t bs, int64_t ld, int64_t m, int c, int hw, int accumulate,
                    void* stream);
 /* dhead (B, A, 64+nc) fp32 rows of one pyramid level -> bf16 dz for the box / cls 1x1 convs
- * (cls zero-padded to a multiple of 8 channels, dz_cls rows of round_up(nc, 8)) and bias grads (+=); nc 1..1024. */
+ * (cls zero-padded to a multiple of 8 channels, dz_cls rows of round_up(nc, 8)) and bias grads; nc 1..1024.
+ * dbias_box [64] / dbias_cls [nc] (either may be NULL) are always ADDED to: there is no accumulate flag. */
 size_t ym_head_grad_workspace_size(void);
 int ym_head_grad(const float* dhead, int64_t a_total, int64_t a_off, int hw, int64_t m, int nc, uint16_t* dz_box,
                  uint16_t* dz_cls, float* dbias_box, float* dbias_cls, float* workspace, size_t workspace_bytes,
