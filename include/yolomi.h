@@ -106,6 +106,26 @@ int ym_eval_detections(const float* pred_boxes, const float* pred_scores, const 
                        int64_t max_gt_per_img, const double* thresholds, int n_thr, int n_ap, int pr_index,
                        float conf, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* Workspace bytes for ym_eval_detections_cls (host only, no GPU needed; non-decreasing in n_pred and nc). */
+size_t ym_eval_cls_workspace_size(int64_t n_img, int64_t n_pred, int n_thr, int nc);
+
+/* Class-aware evaluate_detections: the same algorithm with the label added.  pred_labels (n_pred) and
+ * gt_labels (n_gt) are device int64 arrays of classes in [0, nc), 1 <= nc <= 1024; the other arguments are those
+ * of ym_eval_detections.  A prediction only takes an unmatched GT box of its own label; class c's AP is the
+ * all-point AP of the valid predictions of label c against the number of GT boxes of label c (0 without either).
+ * A class is present when it has a GT box; mAP50 and mAP50-95 are means over the present classes (0 without one),
+ * precision and recall are micro-averaged at pr_index over all classes.
+ * out (device, nc*n_thr + 3*nc + 7 doubles): AP[nc][n_thr], n_gt[nc], tp[nc], fp[nc] (counted at pr_index), then
+ * precision, recall, mAP50, mAP50-95, TP, FP, predictions kept by conf.  A label outside [0, nc) (or an image
+ * over the GT capacity) makes the four metrics and every AP NaN.  Same launches whatever nc and n_img; no host
+ * sync; two calls on one input give identical bits. */
+int ym_eval_detections_cls(const float* pred_boxes, const float* pred_scores, const int64_t* pred_labels,
+                           const int64_t* pred_off, const float* gt_boxes, const int64_t* gt_labels,
+                           const int64_t* gt_off, int64_t n_img, int64_t n_pred, int64_t n_gt,
+                           int64_t max_gt_per_img, int nc, const double* thresholds, int n_thr, int n_ap,
+                           int pr_index, float conf, void* workspace, size_t workspace_bytes, double* out,
+                           void* stream);
+
 /* calculate_ap (utils/metrics.py:277-323) on one flat detection list: scores[n] and
  * is_tp[n] (0/1); workspace ym_eval_workspace_size(1, n, 1).  out (device, 8 doubles):
  * out[0] = AP (0 when n_gt == 0 or n == 0), the rest as ym_eval_detections. */

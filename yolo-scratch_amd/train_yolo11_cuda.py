@@ -28,7 +28,7 @@ sys.path.insert(0, str(Path(__file__).parent))
 from models.yolo11_model import build_yolo11  # noqa: E402
 from losses.yolo_v8_loss import v8DetectionLoss  # noqa: E402
 from datasets import collate_fn_cuda, prepare_batch  # noqa: E402
-from utils.metrics import evaluate_detections  # noqa: E402
+from utils.metrics import evaluate_detections, evaluate_detections_per_class  # noqa: E402
 from yolomi import post as _post  # noqa: E402
 
 collate_fn = collate_fn_cuda
@@ -75,15 +75,33 @@ def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epoc
     return {"loss": s[0], "box_loss": s[1], "cls_loss": s[2], "dfl_loss": s[3]}
 
 
+_PER_CLASS_KEYS = ("ap50", "ap", "n_gt", "tp", "fp")
+
+
+def _head_nc(model):
+    """Class count of the model's Detect head."""
+    for m in reversed(list(model.modules())):
+        if isinstance(getattr(m, "nc", None), int) and hasattr(m, "reg_max"):
+            return m.nc
+    raise ValueError("validate(per_class=True): the model has no Detect head to take nc from; pass nc")
+
+
 @torch.no_grad()
 def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_threshold=0.45, max_batches=None,
-             dp=None):
+             dp=None, per_class=False, nc=None):
     """Validation + metrics (reference :101-262).  Under data parallelism (`dp`, a GradSync) each
     rank evaluates its ValShard of the val set (decode + NMS on its own GPU), the per-image
     detections are gathered to rank 0 in the global image order and evaluate_detections runs there
     (SURVEY §8(e)); the loss sums are all-reduced and the metrics broadcast, so every rank returns
-    the same dict."""
+    the same dict.
+
+    `per_class`: the class-aware evaluation (utils.metrics.evaluate_detections_per_class) over `nc`
+    classes (default: the Detect head's) in place of the reference's class-agnostic one: the same keys
+    hold the class-aware values and "per_class" the per-class lists.  Its detections are decoded from the
+    anchor-major view of the eval output, whose labels are classes."""
     model.eval()
+    if per_class and nc is None:
+        nc = _head_nc(model)
     sums = torch.zeros(4, device=device)
     all_predictions, all_targets = [], []
     batches = 0
@@ -93,13 +111,13 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
         loss, loss_items = criterion(preds, batch)
         sums[0] += loss
         sums[1:] += loss_items
-        if isinstance(preds, tuple) and len(preds) == 2:
-            predictions = decode_predictions_for_metrics(preds[0], batch["img"].shape[-1], conf_threshold,
-                                                         iou_threshold, device)
-        else:
-            decoded = model(batch["img"])
-            predictions = decode_predictions_for_metrics(decoded[0], batch["img"].shape[-1], conf_threshold,
-                                                         iou_threshold, device)
+        decoded = preds[0] if isinstance(preds, tuple) and len(preds) == 2 else model(batch["img"])[0]
+        if per_class:
+            # labels must be classes: decode the anchor-major view (B, A, 4+nc) of the eval output, read in place.
+            # The reference's literal read of (B, 4+nc, A) takes anchors for classes
+            decoded = decoded.transpose(1, 2)
+        predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold, iou_threshold,
+                                                     device)
         all_predictions.extend(predictions)
         bidx, bboxes, cls = batch["batch_idx"], batch["bboxes"], batch["cls"]
         for i in range(batch["img"].shape[0]):
@@ -119,12 +137,25 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
     keys = ("precision", "recall", "mAP50", "mAP50-95")
     if all_predictions is not None:
         # predictions and targets stay in HBM: the metrics run on the GPU (utils/metrics.py)
-        metrics = evaluate_detections(all_predictions, all_targets, conf_threshold=conf_threshold, iou_threshold=0.5)
+        if per_class:
+            metrics = evaluate_detections_per_class(all_predictions, all_targets, nc, conf_threshold=conf_threshold,
+                                                    iou_threshold=0.5)
+        else:
+            metrics = evaluate_detections(all_predictions, all_targets, conf_threshold=conf_threshold,
+                                          iou_threshold=0.5)
     if world > 1:
-        mt = torch.tensor([float(metrics[k]) for k in keys] if all_predictions is not None else [0.0] * 4,
-                          dtype=torch.float64, device=device)
+        vals = [float(metrics[k]) for k in keys] if all_predictions is not None else [0.0] * 4
+        if per_class:                         # the per-class lists travel with the four scalars (counts: exact in fp64)
+            vals += ([float(v) for k in _PER_CLASS_KEYS for v in metrics["per_class"][k]]
+                     if all_predictions is not None else [0.0] * (len(_PER_CLASS_KEYS) * nc))
+        mt = torch.tensor(vals, dtype=torch.float64, device=device)
         tdist.broadcast(mt, 0)
-        metrics = dict(zip(keys, mt.tolist()))
+        mt = mt.tolist()
+        metrics = dict(zip(keys, mt[:4]))
+        if per_class:
+            rows = {k: mt[4 + i * nc: 4 + (i + 1) * nc] for i, k in enumerate(_PER_CLASS_KEYS)}
+            metrics["per_class"] = {k: ([int(v) for v in r] if k in ("n_gt", "tp", "fp") else r)
+                                    for k, r in rows.items()}
     nbatch = float(nb) if (max_batches or world > 1) else len(dataloader)
     s = (sums / max(nbatch, 1)).tolist()
     return {"loss": s[0], "box_loss": s[1], "cls_loss": s[2], "dfl_loss": s[3], **metrics}
@@ -253,7 +284,7 @@ class _SyntheticLoader:
             yield self._mk(i)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Train YOLOv11 for Crater Detection (MI355X)")
     ap.add_argument("--data", type=str, default="/content/data/train")
     ap.add_argument("--cfg", type=str, default=str(Path(__file__).parent / "configs" / "yolo11n_crater.yaml"))
@@ -283,7 +314,13 @@ def main():
     ap.add_argument("--gain", type=float, default=0.4, help="value gain range (+/- fraction; Ultralytics' hsv_v)")
     ap.add_argument("--close-mosaic", type=int, default=10, help="no mosaic in the last N epochs")
     ap.add_argument("--aug-seed", type=int, default=0)
-    args = ap.parse_args()
+    ap.add_argument("--val-per-class", action="store_true",
+                    help="class-aware validation metrics: per-class AP, mAP over the classes with GT")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     from yolomi import dist as ydist
     dp_ctx = ydist.init_from_env()
@@ -351,7 +388,7 @@ def main():
         if dp:
             dp.sync_buffers()          # rank 0's BN running statistics for validation and the checkpoint
         vm = validate(model, val_loader, criterion, device, conf_threshold=args.val_conf, iou_threshold=0.45,
-                      max_batches=args.max_val_batches, dp=dp)
+                      max_batches=args.max_val_batches, dp=dp, per_class=args.val_per_class)
         if not rank0:
             continue
         print(f"\nEpoch {epoch + 1}/{args.epochs} | LR: {lr:.6f}")
@@ -361,7 +398,14 @@ def main():
               f"DFL: {vm['dfl_loss']:.4f}")
         print(f"  Metrics - P: {vm.get('precision', 0.0):.4f}, R: {vm.get('recall', 0.0):.4f}, "
               f"mAP50: {vm.get('mAP50', 0.0):.4f}, mAP50-95: {vm.get('mAP50-95', 0.0):.4f}")
-        ckpt = make_checkpoint(epoch, model, optimizer, tm, vm, best_loss, best_mAP50)
+        if args.val_per_class:
+            pc = vm["per_class"]
+            for c, n in enumerate(pc["n_gt"]):
+                if n > 0:                              # the present classes: the ones the means run over
+                    tp, fp = pc["tp"][c], pc["fp"][c]
+                    print(f"    class {c}: n_gt {n}, P: {tp / (tp + fp) if tp + fp else 0.0:.4f}, R: {tp / n:.4f}, "
+                          f"AP50: {pc['ap50'][c]:.4f}, AP50-95: {pc['ap'][c]:.4f}")
+        ckpt =make_checkpoint(epoch, model, optimizer, tm, vm, best_loss, best_mAP50)
         torch.save(ckpt, save_dir / "last.pt")
         if "mAP50" in vm:
             if vm["mAP50"] > best_mAP50:

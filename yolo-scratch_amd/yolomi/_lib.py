@@ -158,6 +158,8 @@ SIGNATURES = {
     "ym_copy2d": (R, [P, I64, P, I64, I64, I64, P]),
     "ym_eval_workspace_size": (SZ, [I64, I64, INT]),
     "ym_eval_detections": (R, [P, P, P, P, P, I64, I64, I64, I64, P, INT, INT, INT, F32, P, SZ, P, P]),
+    "ym_eval_cls_workspace_size": (SZ, [I64, I64, INT, INT]),
+    "ym_eval_detections_cls": (R, [P, P, P, P, P, P, P, I64, I64, I64, I64, INT, P, INT, INT, INT, F32, P, SZ, P, P]),
     "ym_eval_ap": (R, [P, P, I64, I64, P, SZ, P, P]),
     "ym_iou_matrix": (R, [P, P, I64, I64, P, P]),
     "ym_resize_linear_u8": (R, [P, P, INT, INT, P, P]),
