@@ -509,6 +509,24 @@ int ym_grad_norm(const ym_adamw_entry* table_dev, int n_entries, int64_t total, 
 int ym_adamw(const ym_adamw_entry* table_dev, int n_entries, int64_t total, double lr, double beta1, double beta2,
              double eps, double weight_decay, int64_t step, float max_norm, const float* norm, void* stream);
 
+/* Exponential moving average of the weights (Ultralytics-style ModelEMA.update; the reference has none).
+ * Per element, fp32: e = fma(omd, p - e, e) with omd = (float)one_minus_decay, the difference rounded once.
+ * one_minus_decay in [0, 1]: 0 leaves the EMA untouched (nothing is launched for it), 1 copies p bit for bit.
+ * Flat table as ym_adamw_entry's: offsets ascending from 0, total = sum of n.  No atomics: deterministic. */
+typedef struct {
+    float* ema;
+    const float* src;
+    int64_t offset, n;
+} ym_ema_entry;
+/* ema = ema + (1 - decay) * (src - ema) over a flat table, one launch; src is only read. */
+int ym_ema_update(const ym_ema_entry* table_dev, int n_entries, int64_t total, double one_minus_decay, void* stream);
+/* ym_adamw (p, exp_avg, exp_avg_sq bit-identical to it), and in the same pass ema_dev[e][j] updated from the
+ * parameter value just stored.  ema_dev: device array of n_entries pointers; a NULL pointer skips the EMA for
+ * that entry (nothing of it is read or written). */
+int ym_adamw_ema(const ym_adamw_entry* table_dev, float* const* ema_dev, int n_entries, int64_t total, double lr,
+                 double beta1, double beta2, double eps, double weight_decay, int64_t step, float max_norm,
+                 const float* norm, double one_minus_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,10 +43,11 @@ def _tqdm(it, **kw):
         return it
 
 
-def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epochs, dp=None, augment=None):
+def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epochs, dp=None, augment=None, ema=None):
     """One epoch (reference :31-98).  `dp` is an optional yolomi.dist.GradSync; `augment` an optional
     datasets.BatchAugment, applied in place of prepare_batch (the train and val subsets share one dataset
-    object, so the switch lives in the step: validate never augments)."""
+    object, so the switch lives in the step: validate never augments); `ema` an optional yolomi.ema.ModelEMA,
+    updated after every optimizer step unless the optimizer does that itself (`fuses_ema`)."""
     model.train()
     pbar = _tqdm(dataloader, desc=f"Epoch {epoch}/{epochs}")
     sums = torch.zeros(4, device=device)
@@ -65,6 +66,8 @@ def train_one_epoch(model, dataloader, optimizer, criterion, device, epoch, epoc
         if not getattr(optimizer, "fuses_clip", False):    # FusedAdamW clips on the device itself
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10.0)
         optimizer.step()
+        if ema is not None and not getattr(optimizer, "fuses_ema", False):    # FusedAdamW averages in its pass
+            ema.update()
         sums[0] += loss.detach()
         sums[1:] += loss_items.detach()
         n += 1
@@ -200,12 +203,17 @@ def cosine_lr_schedule(optimizer, epoch, epochs, lr_min=1e-6, lr_max=1e-3, warmu
     return lr
 
 
-def make_checkpoint(epoch, model, optimizer, train_metrics, val_metrics, best_loss, best_mAP50):
+def make_checkpoint(epoch, model, optimizer, train_metrics, val_metrics, best_loss, best_mAP50, ema=None):
     """The reference's checkpoint dict (train_yolo11_cuda.py:628-636), key for key: last.pt / best.pt
-    written by either implementation resume in the other (tests/test_models_cpu.py)."""
-    return {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+    written by either implementation resume in the other (tests/test_models_cpu.py).  With `ema` (a
+    yolomi.ema.ModelEMA) the averaged weights follow as "ema_state_dict" and "ema_updates"; "model_state_dict"
+    stays the raw training weights, so the resume and the reference's loader see what they saw."""
+    ckpt = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
             "train_metrics": train_metrics, "val_metrics": val_metrics, "best_loss": best_loss,
             "best_mAP50": best_mAP50}
+    if ema is not None:
+        ckpt.update(ema.state_dict())
+    return ckpt
 
 
 def _np_safe_globals():
@@ -230,13 +238,19 @@ def _load_np_safe(path, device):
         return torch.load(path, map_location=device, weights_only=True)
 
 
-def resume_checkpoint(path, model, optimizer, device):
+def resume_checkpoint(path, model, optimizer, device, ema=None):
     """Resume as the reference does (:576-586) -> (start_epoch, best_loss, best_mAP50).  Loaded with
     weights_only=True plus the numpy scalar types a reference-written checkpoint holds (its metrics
     are np.float64); the optimizer keeps this process's fused/foreach implementation choice across a
-    reference-written state."""
+    reference-written state.  `ema` (a yolomi.ema.ModelEMA) takes the checkpoint's average and update count;
+    a checkpoint without them (written without --ema, or by the reference) restarts it from the loaded weights."""
     ckpt = _load_np_safe(path, device)
     model.load_state_dict(ckpt["model_state_dict"])
+    if ema is not None:
+        if "ema_state_dict" in ckpt:
+            ema.load_state_dict(ckpt)
+        else:
+            ema.seed(model)
     impl = [{k: g.get(k) for k in ("fused", "foreach")} for g in optimizer.param_groups]
     optimizer.load_state_dict(ckpt["optimizer_state_dict"])
     for g, kv in zip(optimizer.param_groups, impl):
@@ -316,6 +330,11 @@ def build_parser():
     ap.add_argument("--aug-seed", type=int, default=0)
     ap.add_argument("--val-per-class", action="store_true",
                     help="class-aware validation metrics: per-class AP, mAP over the classes with GT")
+    ap.add_argument("--ema", action="store_true",
+                    help="keep an exponential moving average of the weights (yolomi/ema.py): validated and "
+                         "checkpointed as ema_state_dict")
+    ap.add_argument("--ema-decay", type=float, default=0.9999, help="EMA decay once warmed up")
+    ap.add_argument("--ema-tau", type=float, default=2000, help="EMA warm-up: decay * (1 - exp(-updates / tau))")
     return ap
 
 
@@ -361,13 +380,21 @@ def main():
     else:
         optimizer = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     dp = ydist.GradSync(model, dp_ctx) if dp_ctx else None
+    ema = None
+    if args.ema:
+        from yolomi.ema import ModelEMA
+        ema = ModelEMA(model, decay=args.ema_decay, tau=args.ema_tau)
+        if hasattr(optimizer, "attach_ema"):
+            optimizer.attach_ema(ema)      # averaged inside the AdamW pass: no launch of its own per tensor
     start_epoch, best_loss, best_mAP50 = 0, float("inf"), 0.0
     if args.resume and os.path.isfile(args.resume):
-        start_epoch, best_loss, best_mAP50 = resume_checkpoint(args.resume, model, optimizer, device)
+        start_epoch, best_loss, best_mAP50 = resume_checkpoint(args.resume, model, optimizer, device, ema)
         if rank0:
             print(f"Resumed from epoch {start_epoch}, best_loss={best_loss:.4f}, best_mAP50={best_mAP50:.4f}")
     if dp:
         dp.broadcast_state()
+        if ema is not None:                # every rank starts from rank 0's average, as from rank 0's weights
+            ydist.broadcast_buffers(ema.ema, parameters=True)
 
     augment = None
     if args.augment:
@@ -384,11 +411,15 @@ def main():
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
         tm = train_one_epoch(model, train_loader, optimizer, criterion, device, epoch + 1, args.epochs, dp,
-                             augment)
+                             augment, ema)
         if dp:
             dp.sync_buffers()          # rank 0's BN running statistics for validation and the checkpoint
-        vm = validate(model, val_loader, criterion, device, conf_threshold=args.val_conf, iou_threshold=0.45,
-                      max_batches=args.max_val_batches, dp=dp, per_class=args.val_per_class)
+            if ema is not None:
+                ema.sync_buffers(dp)
+        # with --ema the averaged weights are the ones validated (and so the ones best.pt is selected by)
+        vm = validate(ema.refresh() if ema is not None else model, val_loader, criterion, device,
+                      conf_threshold=args.val_conf, iou_threshold=0.45, max_batches=args.max_val_batches, dp=dp,
+                      per_class=args.val_per_class)
         if not rank0:
             continue
         print(f"\nEpoch {epoch + 1}/{args.epochs} | LR: {lr:.6f}")
@@ -405,7 +436,7 @@ def main():
                     tp, fp = pc["tp"][c], pc["fp"][c]
                     print(f"    class {c}: n_gt {n}, P: {tp / (tp + fp) if tp + fp else 0.0:.4f}, R: {tp / n:.4f}, "
                           f"AP50: {pc['ap50'][c]:.4f}, AP50-95: {pc['ap'][c]:.4f}")
-        ckpt =make_checkpoint(epoch, model, optimizer, tm, vm, best_loss, best_mAP50)
+        ckpt = make_checkpoint(epoch, model, optimizer, tm, vm, best_loss, best_mAP50, ema)
         torch.save(ckpt, save_dir / "last.pt")
         if "mAP50" in vm:
             if vm["mAP50"] > best_mAP50:

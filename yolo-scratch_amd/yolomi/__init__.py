@@ -5,5 +5,7 @@ Submodules
   post    decode + NMS postprocess
   graph   NHWC execution plan of the YOLOv11 graph (forward/backward)
   loss    fused assigner + CIoU/DFL/BCE loss kernels
+  optim   clip_grad_norm_ + AdamW in three launches (FusedAdamW)
+  ema     weight EMA, stand-alone or inside FusedAdamW's pass (ModelEMA)
 """
 from ._lib import LIB_PATH, YolomiError, lib  # noqa: F401

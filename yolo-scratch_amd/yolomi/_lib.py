@@ -32,6 +32,11 @@ class AdamWEntry(ctypes.Structure):
     _fields_ = [("p", P), ("g", P), ("m", P), ("v", P), ("offset", I64), ("n", I64)]
 
 
+class EmaEntry(ctypes.Structure):
+    """ym_ema_entry (include/yolomi.h)."""
+    _fields_ = [("ema", P), ("src", P), ("offset", I64), ("n", I64)]
+
+
 class WPrepEntry(ctypes.Structure):
     """ym_wprep_entry (include/yolomi.h)."""
     _fields_ = [("src", P), ("dst_fwd", P), ("dst_t", P), ("elem_offset", I64), ("cout", I32), ("cin", I32),
@@ -167,6 +172,8 @@ SIGNATURES = {
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),
+    "ym_ema_update": (R, [P, INT, I64, F64, P]),
+    "ym_adamw_ema": (R, [P, P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, F64, P]),
 }
 
 _LIB = None

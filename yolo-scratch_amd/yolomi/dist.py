@@ -307,6 +307,15 @@ class GradSync:
                 dist.broadcast(t.data, src)
 
 
+def broadcast_buffers(module: torch.nn.Module, src: int = 0, parameters: bool = False):
+    """Rank `src`'s buffers of any module everywhere: GradSync.sync_buffers for a module a GradSync is not
+    tied to (yolomi.ema.ModelEMA's averaged copy, before validation and the checkpoint).  `parameters`: its
+    parameters as well (GradSync.broadcast_state, once at the start)."""
+    with torch.no_grad():
+        for t in (list(module.parameters()) if parameters else []) + list(module.buffers()):
+            dist.broadcast(t.data, src)
+
+
 # ----------------------------------------------------------------------------- data sharding
 class ValShard(torch.utils.data.Sampler):
     """Validation shard without padding: rank r takes samples r, r + world, ... in order (a

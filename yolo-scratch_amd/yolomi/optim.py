@@ -6,7 +6,9 @@ The reference ends every step with `torch.nn.utils.clip_grad_norm_(model.paramet
 checkpoints resume either way) whose `step()` runs csrc/optim.hip: one deterministic norm of every
 gradient and one streaming AdamW pass over every parameter, the clip coefficient computed on the
 device.  With `max_grad_norm` set it performs the clipping itself (`fuses_clip`); the caller then
-skips clip_grad_norm_.  There is no CPU path: parameters must be fp32 CUDA tensors.
+skips clip_grad_norm_.  With a `yolomi.ema.ModelEMA` attached (`attach_ema`, `fuses_ema`) the same pass keeps the
+weight average up to date as well, and the caller skips `ema.update()`.  There is no CPU path: parameters must be
+fp32 CUDA tensors.
 """
 from __future__ import annotations
 
@@ -24,6 +26,37 @@ class FusedAdamW(torch.optim.AdamW):
         self.last_grad_norm = None        # device scalar: what clip_grad_norm_ would have returned
         self._tables = {}
         self._partials = None
+        self.ema = None                   # a yolomi.ema.ModelEMA updated inside step() (attach_ema)
+        self.fuses_ema = False
+
+    def attach_ema(self, ema):
+        """Maintain `ema` (a yolomi.ema.ModelEMA of the model these parameters belong to) inside step(): the
+        caller then skips ema.update(), as it skips clip_grad_norm_ under `fuses_clip`.  step() counts one EMA
+        update, averages every parameter it steps in the AdamW pass itself (ym_adamw_ema) and the remaining fp32
+        entries of the state dict in one launch after it."""
+        self.ema = ema
+        self.fuses_ema = True
+        self._ema_of = ema.counterparts()
+        self._ema_ptrs = {}
+
+    def _ema_table(self, ps, tag):
+        """Device array of the EMA pointers of the parameters `ps` (NULL where the EMA has none), rebuilt when
+        any pointer changes."""
+        of = self._ema_of
+        try:
+            ptrs = tuple([of[id(p)].data_ptr() for p in ps])
+        except KeyError:                  # a parameter the EMA's model does not hold (or replaced since attach_ema)
+            of = self._ema_of = self.ema.counterparts()
+            ptrs = tuple([of[id(p)].data_ptr() if id(p) in of else 0 for p in ps])
+        hit = self._ema_ptrs.get(tag)
+        if hit is None or hit[0] != ptrs:
+            for p in ps:
+                q = of.get(id(p))
+                if q is not None and not (q.is_cuda and q.dtype == torch.float32 and q.numel() == p.numel()
+                                          and q.is_contiguous()):
+                    raise YolomiError("FusedAdamW: the attached EMA needs fp32 CUDA parameters of the model's shapes")
+            hit = self._ema_ptrs[tag] = (ptrs, torch.tensor(ptrs, dtype=torch.int64).to(ps[0].device))
+        return hit[1]
 
     def _table(self, entries, tag):
         """Device copy of a (p, g, m, v, offset, n) table, rebuilt when any pointer changes."""
@@ -71,7 +104,10 @@ class FusedAdamW(torch.optim.AdamW):
                 torch._foreach_add_(steps, 1.0)
                 groups.append((gi, group, live, steps))
         if not groups:
+            if self.ema is not None:
+                self.ema.update()         # nothing to step: the average still takes its update
             return loss
+        omd = self.ema.advance() if self.ema is not None else None
         s = stream_ptr()
         norm = None
         clip = float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0
@@ -99,7 +135,16 @@ class FusedAdamW(torch.optim.AdamW):
                     st = self.state[p]
                     ents.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
                                  st["exp_avg_sq"].data_ptr(), p.numel()))
-                tab, n, total = self._table(ents, (gi, k) if len(by_step) > 1 else gi)
-                call("ym_adamw", tab.data_ptr(), n, total, lr, float(beta1), float(beta2), float(group["eps"]),
-                     float(group["weight_decay"]), k, clip, norm.data_ptr() if norm is not None else None, s)
+                tag = (gi, k) if len(by_step) > 1 else gi
+                tab, n, total = self._table(ents, tag)
+                if self.ema is None:
+                    call("ym_adamw", tab.data_ptr(), n, total, lr, float(beta1), float(beta2), float(group["eps"]),
+                         float(group["weight_decay"]), k, clip, norm.data_ptr() if norm is not None else None, s)
+                else:
+                    call("ym_adamw_ema", tab.data_ptr(), self._ema_table(ps, tag).data_ptr(), n, total, lr,
+                         float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]), k, clip,
+                         norm.data_ptr() if norm is not None else None, omd, s)
+        if self.ema is not None:
+            # what the pass above did not touch: BatchNorm running statistics, parameters without a gradient
+            self.ema.update_rest(tuple([p.data_ptr() for _, _, live, _ in groups for p in live]), omd)
         return loss
