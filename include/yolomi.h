@@ -83,6 +83,22 @@ int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, int64_t C, in
 int ym_nms(const float* boxes, const float* scores, int64_t n, float iou_thr, void* workspace,
            size_t workspace_bytes, int64_t* keep, int32_t* count, void* stream);
 
+/* Class-aware NMS with a detection cap (an addition: the reference has neither).  Candidates, labels (the first
+ * maximal class) and the order (score descending, filtered index ascending) are ym_decode_nms_strided's; a candidate
+ * is kept iff no earlier KEPT candidate of the SAME label has !(IoU <= iou_thr) with it, the IoU on the true boxes
+ * (no per-class box offset).  Outputs as ym_decode_nms_strided, in global score-descending order across classes.
+ * max_det: 0 no cap, > 0 the first max_det kept boxes per image, < 0 YM_ERR_ARG.
+ * Workspace: ym_nms_cls_workspace_size (>= ym_nms_workspace_size; callable without a GPU). */
+size_t ym_nms_cls_workspace_size(int64_t B, int64_t N);
+int ym_decode_nms_cls(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride, int64_t img_stride,
+                      int64_t col_stride, float conf, float iou_thr, float img_size, int max_det, void* workspace,
+                      size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
+                      int64_t* out_labels, int64_t* out_index, void* stream);
+/* ym_nms with one label per box (any int64 values, compared for equality only; NULL: one class) and the cap:
+ * a batched NMS.  Workspace: ym_nms_cls_workspace_size(1, n). */
+int ym_nms_cls(const float* boxes, const float* scores, const int64_t* labels, int64_t n, float iou_thr, int max_det,
+               void* workspace, size_t workspace_bytes, int64_t* keep, int32_t* count, void* stream);
+
 
 /* ------------------------------------------------------------------ detection metrics
  * Replaces evaluate_detections / calculate_iou_batch / calculate_ap

@@ -1,4 +1,5 @@
-// Decode + class-agnostic greedy NMS, one workgroup per image (gfx950).
+// Decode + greedy NMS (class-agnostic as the reference's, or class-aware with a detection cap: DESIGN §18), one
+// workgroup per image (gfx950).
 //
 // Replaces decode_predictions_for_metrics / nms_simple / calculate_iou_batch_simple
 // (/root/reference/yolo_scratch_cuda/train_yolo11_cuda.py:265-437).  Bit-exact
@@ -40,6 +41,7 @@ struct Ws {
     float4* sbox;     // [B][N] boxes in sorted order      (bitmask path)
     uint64_t* mask;   // [B][N][Wn] suppression bitmask    (bitmask path)
     int32_t* kcount;  // [B] candidates after the filter   (bitmask path)
+    int32_t* slabel;  // [B][N] labels in sorted order     (bitmask path of the class-aware entry points only)
 };
 
 // Bitmask path (small batches: one image is too little work for one workgroup's greedy loop):
@@ -63,7 +65,8 @@ inline size_t bitmask_bytes(int64_t B, int64_t N) {
     return align256(n * 16) + align256(n * wn * 8) + align256(size_t(B) * 4);
 }
 
-inline Ws carve(void* base, int64_t B, int64_t N) {
+// cls: the class-aware entry points' layout, the class-agnostic one plus the sorted labels at its end
+inline Ws carve(void* base, int64_t B, int64_t N, bool cls = false) {
     char* p = static_cast<char*>(base);
     size_t n = size_t(B) * size_t(N);
     Ws w;
@@ -73,12 +76,13 @@ inline Ws carve(void* base, int64_t B, int64_t N) {
     w.flag = reinterpret_cast<int32_t*>(p); p += align256(n * sizeof(int32_t));
     w.frow = reinterpret_cast<int32_t*>(p); p += align256(n * sizeof(int32_t));
     w.keys = reinterpret_cast<uint64_t*>(p); p += align256(size_t(B) * pow2_at_least(N) * 8);
-    w.sbox = nullptr; w.mask = nullptr; w.kcount = nullptr;
+    w.sbox = nullptr; w.mask = nullptr; w.kcount = nullptr; w.slabel = nullptr;
     if (bitmask_path(B, N)) {
         const size_t wn = size_t((N + 63) / 64);
         w.sbox = reinterpret_cast<float4*>(p);   p += align256(n * 16);
         w.mask = reinterpret_cast<uint64_t*>(p); p += align256(n * wn * 8);
-        w.kcount = reinterpret_cast<int32_t*>(p);
+        w.kcount = reinterpret_cast<int32_t*>(p); p += align256(size_t(B) * 4);
+        if (cls) w.slabel = reinterpret_cast<int32_t*>(p);
     }
     return w;
 }
@@ -87,6 +91,10 @@ inline size_t ws_bytes(int64_t B, int64_t N) {
     size_t n = size_t(B) * size_t(N);
     return align256(n * 16) + 4 * align256(n * 4) + align256(size_t(B) * pow2_at_least(N) * 8) + bitmask_bytes(B, N) +
            256;
+}
+
+inline size_t ws_bytes_cls(int64_t B, int64_t N) {
+    return ws_bytes(B, N) + (bitmask_path(B, N) ? align256(size_t(B) * size_t(N) * 4) : 0);
 }
 
 // IoU in the reference's op order (train_yolo11_cuda.py:418-435).
@@ -161,13 +169,15 @@ __global__ void rowmax_wave_kernel(const float* __restrict__ pred, int64_t B, in
     }
 }
 
-// direct candidates (nms_simple): every box is a candidate
-__global__ void direct_kernel(const float4* __restrict__ boxes, const float* __restrict__ scores, int64_t n, Ws w) {
+// direct candidates (nms_simple): every box is a candidate; labels (ym_nms_cls, may be null): their low words go
+// with the candidate, the greedy kernel compares the caller's 64-bit values
+__global__ void direct_kernel(const float4* __restrict__ boxes, const float* __restrict__ scores,
+                              const int64_t* __restrict__ labels, int64_t n, Ws w) {
     int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
     w.box[i] = boxes[i];
     w.score[i] = scores[i];
-    w.label[i] = 0;
+    w.label[i] = labels ? int32_t(labels[i]) : 0;
     w.flag[i] = 1;
 }
 
@@ -230,15 +240,19 @@ __device__ void bitonic(uint64_t* keys, int P) {
 }
 
 // ---------------------------------------------------------------- stage 2
-template <bool SORT_ONLY>
+// CLS: class-aware suppression (a candidate is tested against heads of its own label only; labs[row] of type LT is
+// the label compared, equality only) and the max_det cap (0: none).  The CLS = false instances ignore both.
+template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t>
 __global__ void __launch_bounds__(NMS_THREADS)
 nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp_norm, Ws w,
                  int32_t* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
-                 int64_t* __restrict__ out_labels, int64_t* __restrict__ out_index) {
+                 int64_t* __restrict__ out_labels, int64_t* __restrict__ out_index,
+                 const LT* __restrict__ labs = nullptr, int max_det = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* skeys = reinterpret_cast<uint64_t*>(smem);            // SORT_LDS_KEYS
     __shared__ int sh[NMS_WAVES + 1];
     __shared__ float4 head_box;
+    __shared__ LT head_lab;
     __shared__ int kept_pos_count;
 
     const int64_t b = blockIdx.x;
@@ -291,6 +305,7 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
 
     // c. greedy loop; sorted position s -> filtered index f = keys[s] low bits
     float4 mybox[REG_ITEMS];
+    LT mylab[REG_ITEMS];
     bool alive[REG_ITEMS];
     const bool in_regs = K <= REG_ITEMS * NMS_THREADS;
     if (in_regs) {
@@ -298,9 +313,14 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
         for (int it = 0; it < REG_ITEMS; ++it) {
             int s = tid + it * NMS_THREADS;
             alive[it] = s < K;
+            if constexpr (CLS) {          // the CLS loop evaluates whole waves: no indeterminate operand
+                mybox[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                mylab[it] = LT(0);
+            }
             if (s < K) {
                 int f = int(uint32_t(keys[s]));
                 mybox[it] = w.box[base + w.frow[base + f]];
+                if constexpr (CLS) mylab[it] = labs[base + w.frow[base + f]];
             }
         }
     }
@@ -313,7 +333,8 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
     __syncthreads();
 
     int head = 0;
-    while (head < K) {
+    int nkept = 0;                    // = kept_pos_count, in a register of every thread (one kept box per turn)
+    while (head < K && !(CLS && max_det > 0 && nkept >= max_det)) {
         // record + broadcast the head box: from the registers of the thread that holds sorted
         // position `head` (no dependent global loads on the serial path), or from HBM for K > 8192
         if (in_regs) {
@@ -321,11 +342,15 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
                 const int hit = head / NMS_THREADS;
 #pragma unroll
                 for (int it = 0; it < REG_ITEMS; ++it)
-                    if (it == hit) head_box = mybox[it];
+                    if (it == hit) {
+                        head_box = mybox[it];
+                        if constexpr (CLS) head_lab = mylab[it];
+                    }
             }
         } else if (tid == 0) {
             int f = int(uint32_t(keys[head]));
             head_box = w.box[base + w.frow[base + f]];
+            if constexpr (CLS) head_lab = labs[base + w.frow[base + f]];
         }
         if (tid == 0) {
             out_index[base + kept_pos_count] = head;   // sorted position for now
@@ -333,12 +358,24 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
         }
         __syncthreads();
         const float4 hb = head_box;
+        [[maybe_unused]] LT hl = LT(0);
+        if constexpr (CLS) hl = head_lab;
+        ++nkept;
         int next = INT32_MAX;
         if (in_regs) {
 #pragma unroll
             for (int it = 0; it < REG_ITEMS; ++it) {
                 int s = tid + it * NMS_THREADS;
-                if (alive[it] && s > head) {
+                if constexpr (CLS) {
+                    // the label compare comes first, and the branch is on the whole wave: a wave none of whose
+                    // live boxes has the head's label computes no IoU, and no lane diverges around the division
+                    const bool live = alive[it] && s > head;
+                    const bool test = live && mylab[it] == hl;
+                    bool sup = false;
+                    if (__builtin_amdgcn_ballot_w64(test) != 0) sup = test && !(iou_ref(hb, mybox[it]) <= iou_thr);
+                    alive[it] = live && !sup;
+                    if (alive[it]) next = min(next, s);
+                } else if (alive[it] && s > head) {
                     float v = iou_ref(hb, mybox[it]);
                     if (!(v <= iou_thr)) alive[it] = false;     // reference keeps IoU <= thr (:396)
                     else next = min(next, s);
@@ -350,9 +387,19 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
             for (int s = tid; s < K; s += NMS_THREADS) {
                 if (s > head && galive[s]) {
                     int f = int(uint32_t(keys[s]));
-                    float v = iou_ref(hb, w.box[base + w.frow[base + f]]);
-                    if (!(v <= iou_thr)) galive[s] = 0;
-                    else next = min(next, s);
+                    if constexpr (CLS) {
+                        const int64_t row = base + w.frow[base + f];
+                        // the label first: a candidate of another label loads no box and computes no IoU.  (Loading
+                        // the box beside the label, unconditionally, saves one dependent load where the labels
+                        // match and was 7 % faster with one class, but 1.3x slower with 5 classes and 2.1x with 80:
+                        // DESIGN §18.)
+                        if (labs[row] == hl && !(iou_ref(hb, w.box[row]) <= iou_thr)) galive[s] = 0;
+                        else next = min(next, s);
+                    } else {
+                        float v = iou_ref(hb, w.box[base + w.frow[base + f]]);
+                        if (!(v <= iou_thr)) galive[s] = 0;
+                        else next = min(next, s);
+                    }
                 }
             }
         }
@@ -408,6 +455,7 @@ __global__ void __launch_bounds__(256) nms_rank_kernel(int64_t N, Ws w) {
     if (cnt) atomicAdd(&w.flag[base + i], cnt);
 }
 
+template <bool CLS>
 __global__ void nms_rank_scatter_kernel(int64_t N, int64_t KP, Ws w) {
     const int64_t b = blockIdx.y;
     const int K = w.kcount[b];
@@ -417,14 +465,19 @@ __global__ void nms_rank_scatter_kernel(int64_t N, int64_t KP, Ws w) {
     const int r = w.flag[base + i];
     w.keys[b * KP + r] = cand_key(w, base, i);
     w.sbox[base + r] = w.box[base + w.frow[base + i]];
+    if constexpr (CLS) w.slabel[base + r] = w.label[base + w.frow[base + i]];
 }
 
 // maskT[b][cb][i] bit j-64cb = (j > i) && !(IoU(i, j) <= thr) for sorted positions i, j < K; only
 // cb >= i/64 is written (the scan reads the upper triangle).  Block = 64 rows of one row block.
 // Grid: x = the upper triangle's Wn (Wn + 1) / 2 (row block, column block) pairs, t = cb (cb + 1) / 2 + rb
 // (half the blocks of a square grid, whose lower half only returned), z = image.
+// CLS: the bit also needs label_i == label_j (tested first: another label's pair costs no IoU), so the scan, which
+// only ORs kept rows' words, is class-aware without seeing a label.
+template <bool CLS>
 __global__ void __launch_bounds__(64) nms_mask_kernel(int64_t N, int Wn, float iou_thr, Ws w) {
     __shared__ float4 cols[64];
+    __shared__ int32_t clab[64];
     const int tri = blockIdx.x;
     int cb = int((sqrtf(8.0f * float(tri) + 1.0f) - 1.0f) * 0.5f);
     while (cb * (cb + 1) / 2 > tri) --cb;
@@ -436,16 +489,25 @@ __global__ void __launch_bounds__(64) nms_mask_kernel(int64_t N, int Wn, float i
     const int t = threadIdx.x;
     const int64_t base = b * N;
     const int j0 = cb * 64;
-    if (j0 + t < K) cols[t] = w.sbox[base + j0 + t];
+    if (j0 + t < K) {
+        cols[t] = w.sbox[base + j0 + t];
+        if constexpr (CLS) clab[t] = w.slabel[base + j0 + t];
+    }
     __syncthreads();
     const int i = rb * 64 + t;
     if (i >= K) return;
     const float4 bi = w.sbox[base + i];
+    int32_t li = 0;
+    if constexpr (CLS) li = w.slabel[base + i];
     uint64_t word = 0;
     const int jn = min(64, K - j0);
     for (int jj = 0; jj < jn; ++jj) {
         const int j = j0 + jj;
-        if (j > i && !(iou_ref(bi, cols[jj]) <= iou_thr)) word |= uint64_t(1) << jj;
+        if constexpr (CLS) {
+            if (j > i && clab[jj] == li && !(iou_ref(bi, cols[jj]) <= iou_thr)) word |= uint64_t(1) << jj;
+        } else {
+            if (j > i && !(iou_ref(bi, cols[jj]) <= iou_thr)) word |= uint64_t(1) << jj;
+        }
     }
     w.mask[(b * Wn + cb) * N + i] = word;          // column-major: column cb, row i
 }
@@ -487,12 +549,15 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
 }
 constexpr int SCAN_RB = 8;                          // kept rows per group gathered asynchronously
 
+// CAP: stop at max_det (> 0) kept boxes: the chunk whose alive bits would pass the cap keeps its lowest
+// max_det - nkept of them (sorted order within a chunk is bit order) and the scan ends; later decisions cannot matter.
+template <bool CAP>
 __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP, int Wn, float img_size, Ws w,
                                                            int32_t* __restrict__ out_count,
                                                            float* __restrict__ out_boxes,
                                                            float* __restrict__ out_scores,
                                                            int64_t* __restrict__ out_labels,
-                                                           int64_t* __restrict__ out_index) {
+                                                           int64_t* __restrict__ out_index, int max_det = 0) {
     __shared__ int rows_sh[256];
     const int64_t b = blockIdx.x;
     const int lane = threadIdx.x;
@@ -542,8 +607,9 @@ __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP
 #pragma unroll
         for (int k = 0; k < SCAN_WL; ++k) pend[r][k] = 0;
     int nkept = 0;
+    bool full = false;                                // CAP: max_det boxes are kept
     load_group(0, dcur);
-    for (int g = 0; g < ngr; ++g) {
+    for (int g = 0; g < ngr && !full; ++g) {
         // Everything loaded at the previous group's start (this group's D blocks, the far words of
         // group g-2's kept rows) has had a whole group of decisions to arrive: wait for it HERE, once,
         // explicitly.  (Left to the compiler, the loop-carried loads got conservative vmcnt waits
@@ -619,13 +685,29 @@ __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP
                 alive |= uint64_t(1) << sl;
                 und &= ~readlane64(diag, sl) & ~(uint64_t(1) << sl);
             }
+            if constexpr (CAP) {
+                if (nkept + __popcll(alive) >= max_det) {
+                    uint64_t rest = alive;
+                    alive = 0;
+                    for (int m = max_det - nkept; m > 0; --m) {     // the lowest max_det - nkept alive bits
+                        alive |= rest & (~rest + 1);
+                        rest &= rest - 1;
+                    }
+                    full = true;
+                }
+            }
             if ((alive >> lane) & 1) out_index[base + nkept + __popcll(alive & ((uint64_t(1) << lane) - 1))] = 64 * c + lane;
             nkept += __popcll(alive);
             kcur[q] = alive;
+            if constexpr (CAP)
+                if (full) break;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) kprev[q] = kcur[q];
     }
+    // CAP: the early stop leaves this group's dnx / pend loads in flight; nothing reads them, drain them before
+    // the registers are reused below
+    if constexpr (CAP) __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();                                 // this wave's out_index stores are visible to its loads
     // outputs in kept order (sorted position -> filtered index -> row)
     for (int k = lane; k < nkept; k += 64) {
@@ -645,28 +727,51 @@ __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP
     if (lane == 0) out_count[b] = nkept;
 }
 
+// cls: the class-aware instances with the max_det cap (0: none); lab64: the caller's 64-bit labels by row (ym_nms_cls),
+// null: w.label.  The class-agnostic entry points launch the CLS = false / CAP = false instances.
 int launch_nms(int64_t B, int64_t Nalloc, float iou_thr, float img_size, int clamp_norm, Ws w,
                int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
-               hipStream_t st) {
+               hipStream_t st, bool cls = false, int max_det = 0, const int64_t* lab64 = nullptr) {
     size_t lds = size_t(SORT_LDS_KEYS) * sizeof(uint64_t);
     if (w.mask && clamp_norm) {
         const int Wn = int((Nalloc + 63) / 64);
         const int64_t KP = pow2_at_least(Nalloc);
-        hipLaunchKernelGGL(nms_image_kernel<true>, dim3(unsigned(B)), dim3(NMS_THREADS), lds, st, Nalloc, KP, iou_thr,
-                           img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels, out_index);
+        // (the compaction never reads a label: one instance serves both)
+        hipLaunchKernelGGL((nms_image_kernel<true, false, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
+                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
+                           out_index, static_cast<const int32_t*>(nullptr), 0);
         const unsigned nt = unsigned((Nalloc + 255) / 256);
         hipLaunchKernelGGL(nms_rank_kernel, dim3(nt, nt, unsigned(B)), dim3(256), 0, st, Nalloc, w);
-        hipLaunchKernelGGL(nms_rank_scatter_kernel, dim3(nt, unsigned(B)), dim3(256), 0, st, Nalloc, KP, w);
-        hipLaunchKernelGGL(nms_mask_kernel, dim3(unsigned(Wn * (Wn + 1) / 2), 1, unsigned(B)), dim3(64), 0, st, Nalloc,
-                           Wn, iou_thr, w);
-        hipLaunchKernelGGL(nms_scan_wave_kernel, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn, img_size, w,
-                           out_count, out_boxes, out_scores, out_labels, out_index);
+        const dim3 mgrid(unsigned(Wn * (Wn + 1) / 2), 1, unsigned(B));
+        if (cls) {
+            hipLaunchKernelGGL(nms_rank_scatter_kernel<true>, dim3(nt, unsigned(B)), dim3(256), 0, st, Nalloc, KP, w);
+            hipLaunchKernelGGL(nms_mask_kernel<true>, mgrid, dim3(64), 0, st, Nalloc, Wn, iou_thr, w);
+        } else {
+            hipLaunchKernelGGL(nms_rank_scatter_kernel<false>, dim3(nt, unsigned(B)), dim3(256), 0, st, Nalloc, KP, w);
+            hipLaunchKernelGGL(nms_mask_kernel<false>, mgrid, dim3(64), 0, st, Nalloc, Wn, iou_thr, w);
+        }
+        if (cls && max_det > 0)
+            hipLaunchKernelGGL(nms_scan_wave_kernel<true>, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn, img_size,
+                               w, out_count, out_boxes, out_scores, out_labels, out_index, max_det);
+        else
+            hipLaunchKernelGGL(nms_scan_wave_kernel<false>, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn,
+                               img_size, w, out_count, out_boxes, out_scores, out_labels, out_index, 0);
         YM_LAUNCH_CHECK("nms bitmask path");
         return YM_OK;
     }
-    hipLaunchKernelGGL(nms_image_kernel<false>, dim3(unsigned(B)), dim3(NMS_THREADS), lds, st, Nalloc,
-                       pow2_at_least(Nalloc), iou_thr, img_size,
-                       clamp_norm, w, out_count, out_boxes, out_scores, out_labels, out_index);
+    const int64_t KP = pow2_at_least(Nalloc);
+    if (cls && lab64)
+        hipLaunchKernelGGL((nms_image_kernel<false, true, int64_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
+                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
+                           out_index, lab64, max_det);
+    else if (cls)
+        hipLaunchKernelGGL((nms_image_kernel<false, true, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
+                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
+                           out_index, static_cast<const int32_t*>(w.label), max_det);
+    else
+        hipLaunchKernelGGL((nms_image_kernel<false, false, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
+                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
+                           out_index, static_cast<const int32_t*>(nullptr), 0);
     YM_LAUNCH_CHECK("nms_image_kernel");
     return YM_OK;
 }
@@ -693,10 +798,12 @@ extern "C" int ym_iou_row(const float* box1, const float* boxes2, int64_t m, flo
     return YM_OK;
 }
 
-extern "C" int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
-                                     int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_size,
-                                     void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
-                                     float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream) {
+// cls: ym_decode_nms_cls (its workspace layout, the class-aware kernels, the max_det cap)
+static int decode_nms_impl(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride, int64_t img_stride,
+                           int64_t col_stride, float conf, float iou_thr, float img_size, bool cls, int max_det,
+                           void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                           float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream) {
+    YM_CHECK_ARG(max_det >= 0, "ym_decode_nms_cls: max_det %d < 0", max_det);
     YM_CHECK_ARG(B >= 0 && N >= 0 && C >= 1, "ym_decode_nms: bad shape B=%lld N=%lld C=%lld", (long long)B,
                  (long long)N, (long long)C);
     YM_CHECK_ARG(col_stride >= 1 && (col_stride > 1 || row_stride >= 4 + C), "ym_decode_nms: row_stride < 4+C");
@@ -704,9 +811,9 @@ extern "C" int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, in
     if (B == 0) return YM_OK;
     hipStream_t st = as_stream(stream);
     if (N == 0) return hipMemsetAsync(out_count, 0, B * sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
-    YM_CHECK_ARG(workspace_bytes >= ws_bytes(B, N), "ym_decode_nms: workspace too small (%zu < %zu)",
-                 workspace_bytes, ws_bytes(B, N));
-    Ws w = carve(workspace, B, N);
+    const size_t need = cls ? ws_bytes_cls(B, N) : ws_bytes(B, N);
+    YM_CHECK_ARG(workspace_bytes >= need, "ym_decode_nms: workspace too small (%zu < %zu)", workspace_bytes, need);
+    Ws w = carve(workspace, B, N, cls);
     if (C <= 64)
         hipLaunchKernelGGL(rowmax_thread_kernel, dim3(unsigned((B * N + 255) / 256)), dim3(256), 0, st, pred, B, N,
                            C, row_stride, img_stride, col_stride, conf, w);
@@ -714,7 +821,27 @@ extern "C" int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, in
         hipLaunchKernelGGL(rowmax_wave_kernel, dim3(unsigned((B * N + 3) / 4)), dim3(256), 0, st, pred, B, N, C,
                            row_stride, img_stride, col_stride, conf, w);
     YM_LAUNCH_CHECK("rowmax");
-    return launch_nms(B, N, iou_thr, img_size, 1, w, out_count, out_boxes, out_scores, out_labels, out_index, st);
+    return launch_nms(B, N, iou_thr, img_size, 1, w, out_count, out_boxes, out_scores, out_labels, out_index, st, cls,
+                      max_det);
+}
+
+extern "C" int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
+                                     int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_size,
+                                     void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                                     float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream) {
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, false, 0,
+                           workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index, stream);
+}
+
+extern "C" size_t ym_nms_cls_workspace_size(int64_t B, int64_t N) { return 2 * ws_bytes_cls(B, N); }
+
+extern "C" int ym_decode_nms_cls(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
+                                 int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_size,
+                                 int max_det, void* workspace, size_t workspace_bytes, int32_t* out_count,
+                                 float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
+                                 void* stream) {
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, true, max_det,
+                           workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index, stream);
 }
 
 extern "C" int ym_decode_nms(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
@@ -725,9 +852,12 @@ extern "C" int ym_decode_nms(const float* pred, int64_t B, int64_t N, int64_t C,
                                  workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index, stream);
 }
 
-extern "C" int ym_nms(const float* boxes, const float* scores, int64_t n, float iou_thr, void* workspace,
-                      size_t workspace_bytes, int64_t* keep, int32_t* count, void* stream) {
+// cls: ym_nms_cls (labels, null: one class; max_det).  Both use ym_nms's workspace layout.
+static int nms_impl(const float* boxes, const float* scores, const int64_t* labels, int64_t n, float iou_thr, bool cls,
+                    int max_det, void* workspace, size_t workspace_bytes, int64_t* keep, int32_t* count,
+                    void* stream) {
     YM_CHECK_ARG(n >= 0, "ym_nms: n < 0");
+    YM_CHECK_ARG(max_det >= 0, "ym_nms_cls: max_det %d < 0", max_det);
     hipStream_t st = as_stream(stream);
     if (n == 0) return hipMemsetAsync(count, 0, sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
     YM_CHECK_ARG(workspace_bytes >= ws_bytes(1, n) + ws_bytes(1, n), "ym_nms: workspace too small");
@@ -738,7 +868,18 @@ extern "C" int ym_nms(const float* boxes, const float* scores, int64_t n, float 
     float* os = reinterpret_cast<float*>(extra + align256(n * 16));
     int64_t* ol = reinterpret_cast<int64_t*>(extra + align256(n * 16) + align256(n * 4));
     hipLaunchKernelGGL(direct_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(boxes), scores, n, w);
+                       reinterpret_cast<const float4*>(boxes), scores, labels, n, w);
     YM_LAUNCH_CHECK("nms direct");
-    return launch_nms(1, n, iou_thr, 1.0f, 0, w, count, ob, os, ol, keep, st);
+    return launch_nms(1, n, iou_thr, 1.0f, 0, w, count, ob, os, ol, keep, st, cls, max_det, labels);
+}
+
+extern "C" int ym_nms(const float* boxes, const float* scores, int64_t n, float iou_thr, void* workspace,
+                      size_t workspace_bytes, int64_t* keep, int32_t* count, void* stream) {
+    return nms_impl(boxes, scores, nullptr, n, iou_thr, false, 0, workspace, workspace_bytes, keep, count, stream);
+}
+
+extern "C" int ym_nms_cls(const float* boxes, const float* scores, const int64_t* labels, int64_t n, float iou_thr,
+                          int max_det, void* workspace, size_t workspace_bytes, int64_t* keep, int32_t* count,
+                          void* stream) {
+    return nms_impl(boxes, scores, labels, n, iou_thr, true, max_det, workspace, workspace_bytes, keep, count, stream);
 }

@@ -91,7 +91,7 @@ def _head_nc(model):
 
 @torch.no_grad()
 def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_threshold=0.45, max_batches=None,
-             dp=None, per_class=False, nc=None):
+             dp=None, per_class=False, nc=None, nms_per_class=False, max_det=0):
     """Validation + metrics (reference :101-262).  Under data parallelism (`dp`, a GradSync) each
     rank evaluates its ValShard of the val set (decode + NMS on its own GPU), the per-image
     detections are gathered to rank 0 in the global image order and evaluate_detections runs there
@@ -101,7 +101,16 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
     `per_class`: the class-aware evaluation (utils.metrics.evaluate_detections_per_class) over `nc`
     classes (default: the Detect head's) in place of the reference's class-agnostic one: the same keys
     hold the class-aware values and "per_class" the per-class lists.  Its detections are decoded from the
-    anchor-major view of the eval output, whose labels are classes."""
+    anchor-major view of the eval output, whose labels are classes.
+
+    `nms_per_class` (needs `per_class`: only that read has classes for labels): class-aware NMS, a box is
+    suppressed by kept boxes of its own class only, and at most `max_det` boxes per image (0: no cap), the
+    usual YOLO evaluation recipe.  The result's keys do not change."""
+    if nms_per_class and not per_class:
+        raise ValueError("validate(nms_per_class=True) needs per_class=True: the reference's literal read of the "
+                         "eval output has anchor indices for labels, and suppression by those means nothing")
+    if max_det and not nms_per_class:
+        raise ValueError("validate(max_det=N) needs nms_per_class=True: the class-agnostic NMS has no cap")
     model.eval()
     if per_class and nc is None:
         nc = _head_nc(model)
@@ -119,8 +128,12 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
             # labels must be classes: decode the anchor-major view (B, A, 4+nc) of the eval output, read in place.
             # The reference's literal read of (B, 4+nc, A) takes anchors for classes
             decoded = decoded.transpose(1, 2)
-        predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold, iou_threshold,
-                                                     device)
+        if nms_per_class:
+            predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold,
+                                                         iou_threshold, device, class_aware=True, max_det=max_det)
+        else:
+            predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold,
+                                                         iou_threshold, device)
         all_predictions.extend(predictions)
         bidx, bboxes, cls = batch["batch_idx"], batch["bboxes"], batch["cls"]
         for i in range(batch["img"].shape[0]):
@@ -164,14 +177,19 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
     return {"loss": s[0], "box_loss": s[1], "cls_loss": s[2], "dfl_loss": s[3], **metrics}
 
 
-def decode_predictions_for_metrics(preds, img_size, conf_threshold, iou_threshold, device):
+def decode_predictions_for_metrics(preds, img_size, conf_threshold, iou_threshold, device, class_aware=False,
+                                   max_det=0):
     """Per-image boxes/scores/labels (normalised xyxy) from decoded predictions.
 
     Reads `preds` as (batch, rows, 4+C) exactly like the reference (:289-301),
     including when it is handed the (B, 4+nc, A) eval tensor.
     One batched GPU launch pair; one host sync for the per-image counts.
+    `class_aware` / `max_det`: class-aware NMS with a detection cap (yolomi.post.decode_nms).
     """
     pred = preds[0] if isinstance(preds, tuple) and len(preds) == 2 else preds
+    if class_aware or max_det:
+        return _post.decode_nms(pred, img_size, conf_threshold, iou_threshold, class_aware=class_aware,
+                                max_det=max_det)
     return _post.decode_nms(pred, img_size, conf_threshold, iou_threshold)
 
 
@@ -298,8 +316,21 @@ class _SyntheticLoader:
             yield self._mk(i)
 
 
+class _Parser(argparse.ArgumentParser):
+    """Checks the combinations of flags argparse cannot express."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if ns.val_nms_per_class and not ns.val_per_class:
+            self.error("--val-nms-per-class needs --val-per-class (only the class-aware evaluation decodes class "
+                       "labels)")
+        if ns.val_max_det < 0 or (ns.val_max_det and not ns.val_nms_per_class):
+            self.error("--val-max-det N needs N >= 0 and --val-nms-per-class")
+        return ns, rest
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(description="Train YOLOv11 for Crater Detection (MI355X)")
+    ap = _Parser(description="Train YOLOv11 for Crater Detection (MI355X)")
     ap.add_argument("--data", type=str, default="/content/data/train")
     ap.add_argument("--cfg", type=str, default=str(Path(__file__).parent / "configs" / "yolo11n_crater.yaml"))
     ap.add_argument("--scale", type=str, default="s", choices=["n", "s", "m", "l", "x"])
@@ -330,6 +361,11 @@ def build_parser():
     ap.add_argument("--aug-seed", type=int, default=0)
     ap.add_argument("--val-per-class", action="store_true",
                     help="class-aware validation metrics: per-class AP, mAP over the classes with GT")
+    ap.add_argument("--val-nms-per-class", action="store_true",
+                    help="class-aware NMS in validation (needs --val-per-class): a box is suppressed by boxes of its "
+                         "own class only")
+    ap.add_argument("--val-max-det", type=int, default=0,
+                    help="keep at most N boxes per image after the class-aware NMS (0: no cap)")
     ap.add_argument("--ema", action="store_true",
                     help="keep an exponential moving average of the weights (yolomi/ema.py): validated and "
                          "checkpointed as ema_state_dict")
@@ -419,7 +455,7 @@ def main():
         # with --ema the averaged weights are the ones validated (and so the ones best.pt is selected by)
         vm = validate(ema.refresh() if ema is not None else model, val_loader, criterion, device,
                       conf_threshold=args.val_conf, iou_threshold=0.45, max_batches=args.max_val_batches, dp=dp,
-                      per_class=args.val_per_class)
+                      per_class=args.val_per_class, nms_per_class=args.val_nms_per_class, max_det=args.val_max_det)
         if not rank0:
             continue
         print(f"\nEpoch {epoch + 1}/{args.epochs} | LR: {lr:.6f}")

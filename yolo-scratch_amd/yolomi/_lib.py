@@ -79,6 +79,9 @@ SIGNATURES = {
     "ym_decode_nms": (R, [P, I64, I64, I64, I64, I64, F32, F32, F32, P, SZ, P, P, P, P, P, P]),
     "ym_decode_nms_strided": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, P, SZ, P, P, P, P, P, P]),
     "ym_nms": (R, [P, P, I64, F32, P, SZ, P, P, P]),
+    "ym_nms_cls_workspace_size": (SZ, [I64, I64]),
+    "ym_decode_nms_cls": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, INT, P, SZ, P, P, P, P, P, P]),
+    "ym_nms_cls": (R, [P, P, P, I64, F32, INT, P, SZ, P, P, P]),
     "ym_conv_stat_blocks": (R, [I64, INT]),
     "ym_conv_fwd_stat_rows": (R, [P]),
     "ym_conv_algo": (R, [P, INT]),

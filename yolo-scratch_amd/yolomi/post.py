@@ -21,24 +21,44 @@ def iou_row(box1: torch.Tensor, boxes2: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
-    """Keep indices (int64, device) in kept order."""
+def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float, labels: torch.Tensor | None = None,
+        max_det: int = 0) -> torch.Tensor:
+    """Keep indices (int64, device) in kept order.
+
+    `labels` (any integer values, one per box): a box is suppressed by boxes of its own label only (batched NMS,
+    ym_nms_cls); `max_det` > 0: the first `max_det` kept indices.  With the defaults: ym_nms."""
     require_device(boxes, scores)
     from ._lib import lib
     n = boxes.shape[0]
     b = boxes.float().contiguous()
     s = scores.float().contiguous()
-    ws_bytes = lib().ym_nms_workspace_size(1, max(n, 1))
+    cls = labels is not None or max_det != 0
+    ws_bytes = (lib().ym_nms_cls_workspace_size if cls else lib().ym_nms_workspace_size)(1, max(n, 1))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=b.device)
     keep = torch.empty(max(n, 1), dtype=torch.int64, device=b.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=b.device)
-    call("ym_nms", ptr(b), ptr(s), n, float(iou_threshold), ptr(ws), ws_bytes, ptr(keep), ptr(cnt),
-         stream_ptr(b.device))
+    if cls:
+        lab = None
+        if labels is not None:
+            require_device(labels)
+            if labels.shape[0] != n:
+                raise ValueError(f"nms: {labels.shape[0]} labels for {n} boxes")
+            lab = labels.reshape(-1).to(torch.int64).contiguous()
+        call("ym_nms_cls", ptr(b), ptr(s), ptr(lab), n, float(iou_threshold), int(max_det), ptr(ws), ws_bytes,
+             ptr(keep), ptr(cnt), stream_ptr(b.device))
+    else:
+        call("ym_nms", ptr(b), ptr(s), n, float(iou_threshold), ptr(ws), ws_bytes, ptr(keep), ptr(cnt),
+             stream_ptr(b.device))
     return keep[: int(cnt.item())]
 
 
-def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float):
-    """Batched decode+NMS of pred read as (B, N, 4+C).  Returns per-image dicts."""
+def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_aware: bool = False,
+               max_det: int = 0):
+    """Batched decode+NMS of pred read as (B, N, 4+C).  Returns per-image dicts.
+
+    `class_aware`: a candidate is suppressed by kept candidates of its own label only; `max_det` > 0: at most that
+    many boxes per image, the best-scoring kept ones (ym_decode_nms_cls).  With the defaults: the
+    reference's class-agnostic NMS (ym_decode_nms_strided)."""
     require_device(pred)
     from ._lib import lib
     p = pred.float()
@@ -47,7 +67,9 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float):
     B, N, W = p.shape
     C = W - 4
     dev = p.device
-    ws_bytes = lib().ym_nms_workspace_size(B, max(N, 1))
+    if max_det and not class_aware:
+        raise ValueError("decode_nms: max_det needs class_aware=True (the class-agnostic path has no cap)")
+    ws_bytes = (lib().ym_nms_cls_workspace_size if class_aware else lib().ym_nms_workspace_size)(B, max(N, 1))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     cnt = torch.empty(B, dtype=torch.int32, device=dev)          # every count is written by the launch
     boxes = torch.empty(B, N, 4, dtype=torch.float32, device=dev)
@@ -55,8 +77,13 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float):
     labels = torch.empty(B, N, dtype=torch.int64, device=dev)
     index = torch.empty(B, N, dtype=torch.int64, device=dev)
     # a row's elements may be strided (the anchor-major view y.transpose(1, 2) of the eval output): read in place
-    call("ym_decode_nms_strided", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf), float(iou_thr),
-         float(img_size), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores), ptr(labels), ptr(index),
-         stream_ptr(dev))
+    if class_aware:
+        call("ym_decode_nms_cls", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf),
+             float(iou_thr), float(img_size), int(max_det), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores),
+             ptr(labels), ptr(index), stream_ptr(dev))
+    else:
+        call("ym_decode_nms_strided", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf),
+             float(iou_thr), float(img_size), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores), ptr(labels),
+             ptr(index), stream_ptr(dev))
     counts = cnt.cpu().tolist()                      # the single host sync of the batch
     return [{"boxes": boxes[b, :k], "scores": scores[b, :k], "labels": labels[b, :k]} for b, k in enumerate(counts)]
