@@ -153,6 +153,55 @@ def _split_policy_defaults(L):
         L.ym_conv_set_eval_split(prev)
 
 
+def test_conv_fwd_eval_workspace_from_another_setting():
+    """yolomi_experimental.h: a workspace sized under one setting and passed to a call made under another is checked by
+    that call.  (1, 20, 20, 136, 64, 3, 1) splits into 6 slices under eval cfg 1 (27 64-deep K stages) and into 11
+    under cfg 0 (45 32-deep ones).  The 6-slice workspace given to a call under cfg 0 is too small: the call runs
+    unsplit and touches neither the workspace nor the 4 KiB after it.  The 11-slice workspace given to a call under
+    cfg 1 serves its 6 slices; the guard after it stays intact.  Both results match torch at this file's tolerance."""
+    from yolomi._lib import call, lib, stream_ptr
+    L = lib()
+    n, h, w, cin, cout, k, s = case = (1, 20, 20, 136, 64, 3, 1)
+    d, oh, ow = _desc(n, h, w, cin, cout, k, s, cout)
+    g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
+    x = torch.randn(n, h, w, cin, generator=g).half()
+    wt = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).half()
+    scale = torch.rand(cout, generator=g) + 0.5
+    shift = torch.randn(cout, generator=g) * 0.2
+    ref = F.conv2d(x.float().permute(0, 3, 1, 2), wt.float(), stride=s, padding=k // 2).permute(0, 2, 3, 1)
+    ref = F.silu(ref * scale + shift)
+    mag = float(ref.abs().max())
+    dev = torch.device("cuda")
+    xd, wd, scd, shd = x.to(dev), wt.permute(0, 2, 3, 1).contiguous().to(dev), scale.to(dev), shift.to(dev)
+    GUARD = 4096
+
+    def run(size_cfg, call_cfg):
+        L.ym_conv_set_eval_cfg(size_cfg)
+        nws = L.ym_conv_fwd_eval_workspace_size(ctypes.byref(d))
+        ws = torch.full((nws + GUARD,), 255, dtype=torch.uint8, device=dev)
+        y = torch.zeros(n, oh, ow, cout, dtype=torch.float16, device=dev)
+        L.ym_conv_set_eval_cfg(call_cfg)
+        torch.cuda.synchronize()
+        call("ym_conv_fwd_eval", ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), scd.data_ptr(), shd.data_ptr(), 1, None,
+             0, 0, y.data_ptr(), ws.data_ptr(), nws, stream_ptr(dev))
+        torch.cuda.synchronize()
+        err = float((y.float().cpu() - ref).abs().max())
+        assert err <= 2e-3 * mag + 1e-3, f"max |diff| {err:.3e} vs max |ref| {mag:.3e}"
+        return nws, ws.cpu()
+
+    prev = L.ym_conv_set_eval_cfg(-1)
+    try:
+        slab = oh * ow * cout * 4
+        nws, ws = run(1, 0)
+        assert nws == 6 * slab
+        assert bool((ws == 255).all()), "an unsplit call wrote the workspace or past it"
+        nws, ws = run(0, 1)
+        assert nws == 11 * slab
+        assert bool((ws[nws:] == 255).all()), "the guard after the workspace was written"
+    finally:
+        L.ym_conv_set_eval_cfg(prev)
+
+
 @pytest.mark.parametrize("scale_name,imgsz,bs", [("s", 640, 1), ("n", 320, 2)])
 def test_eval_forward_one_launch_blocks_vs_unfused(scale_name, imgsz, bs, monkeypatch):
     """The eval forward with the one-launch Conv blocks (default) against the same model with them off

@@ -610,11 +610,14 @@ static int fold_blocks(int64_t m, int c) {
     return std::min(256, std::max(FOLD_GP, 512 / (c / 64)));
 }
 
-extern "C" int ym_bn_bwd_fold_ok(int64_t m, int c) {
-    if (g_bwd_fold == 0) return 0;
-    const int64_t cap = g_bwd_fold == 1 ? FOLD_MAX_M : FOLD_MAX_M2;
-    return m > 0 && m <= cap && c % 64 == 0 && c <= 2048 && ym_bn_bwd_blocks(m, c) >= fold_blocks(m, c) ? 1 : 0;
+// mode: g_bwd_fold as the entry point read it (once)
+static bool bwd_fold_ok(int mode, int64_t m, int c) {
+    if (mode == 0) return false;
+    const int64_t cap = mode == 1 ? FOLD_MAX_M : FOLD_MAX_M2;
+    return m > 0 && m <= cap && c % 64 == 0 && c <= 2048 && ym_bn_bwd_blocks(m, c) >= fold_blocks(m, c);
 }
+
+extern "C" int ym_bn_bwd_fold_ok(int64_t m, int c) { return bwd_fold_ok(g_bwd_fold, m, c) ? 1 : 0; }
 
 extern "C" int ym_bn_set_bwd_fold(int mode) {
     // fused backward statistics + finalize: -1 default (= 2), 0 off, 1 on up to 25600 pixels, 2 up to 102400;
@@ -630,7 +633,7 @@ extern "C" int ym_bn_bwd_reduce_fold(const uint16_t* dy, int64_t d_bs, int64_t d
     CHECK_C(c);
     CHECK_VIEW(d_bs, d_ld, hw);
     YM_CHECK_ARG(workspace && gamma && coef, "ym_bn_bwd_reduce_fold: null argument");
-    if (!ym_bn_bwd_fold_ok(m, c)) {
+    if (!bwd_fold_ok(g_bwd_fold, m, c)) {
         // the streaming statistics kernel + the finalize launch (the same outputs)
         const int r = ym_bn_bwd_reduce(dy, d_bs, d_ld, z, m, c, hw, scale, shift, mean, rstd, act, part_sum, part_dot,
                                        stream);

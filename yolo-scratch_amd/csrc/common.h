@@ -51,13 +51,6 @@ struct Policy {
     }
 };
 
-// Conv kernel selection batch (ym_conv_set_select_batch): when > 0 the selection rules of every conv
-// kernel (size thresholds, tile shapes) evaluate as if the batch held this many images, while the
-// launch geometry still follows the real batch — so a small-batch parity test runs exactly the kernel
-// instances a large-batch training step selects.  0 (the default): the real batch.
-extern Policy g_select_n;
-static inline int64_t select_n(const ym_conv_desc* d) { return g_select_n > 0 ? int64_t(g_select_n) : int64_t(d->n); }
-
 // the weight-gradient kernel instance ym_conv_wgrad runs for d (wgrad.hip; ym_conv_kernel dir 2)
 int wgrad_kernel(const ym_conv_desc* d, char* name, size_t len);
 

@@ -38,7 +38,6 @@
 #include "tile.h"
 
 namespace ym {
-Policy g_select_n{0};
 std::atomic<unsigned> g_policy_gen{0};
 
 namespace {
@@ -1105,19 +1104,8 @@ static int launch_tile(const GemmArgs& a, Tile t, int max_blocks, hipStream_t st
                                      : launch_tile_k<64, 2, MODE>(a, t, max_blocks, st);
 }
 
-// nsel: the batch the tile choice is made for (select_n: the real batch unless a parity test pins the
-// selection of a larger one)
-static int pick_and_launch(GemmArgs a, int mode, int max_blocks, int64_t nsel, hipStream_t st) {
-    const int os = a.ostep;
-    const int64_t Mc = nsel * ((a.OH + os - 1) / os) * ((a.OW + os - 1) / os);
-    const Tile t = pick_tile(Mc, os == 2 ? 4 : 1, a.Nout);
-    return mode == MODE_FWD ? launch_tile<MODE_FWD>(a, t, max_blocks, st) : launch_tile<MODE_DGRAD>(a, t, max_blocks, st);
-}
-
-// rows of the BN statistics partials of the 2-stage implicit GEMM's forward: M output pixels, the tile
-// chosen for Msel of them
-static int gemm_stat_rows(int64_t M, int64_t Msel, int Cout) {
-    const Tile t = pick_tile(Msel, 1, Cout);
+// rows of the BN statistics partials of the 2-stage implicit GEMM's forward: M output pixels on tile t
+static int gemm_stat_rows(int64_t M, Tile t, int Cout) {
     const int mtiles = int((M + t.bm - 1) / t.bm);
     return grid_x(mtiles, (Cout + t.bn - 1) / t.bn, true, FWD_STAT_BLOCKS);
 }
@@ -1125,8 +1113,14 @@ static int gemm_stat_rows(int64_t M, int64_t Msel, int Cout) {
 extern "C" int ym_conv_stat_blocks(int64_t M, int Cout) {
     // grid-x of the 2-stage implicit GEMM's statistics partials (the generic kernel only; the row count of
     // any conv forward is ym_conv_fwd_stat_rows)
-    return gemm_stat_rows(M, M, Cout);
+    return gemm_stat_rows(M, pick_tile(M, 1, Cout), Cout);
 }
+
+// The conv selection policies (yolomi_experimental.h) are static here, each next to its setter.  Nothing but the
+// setters and ConvPolicy::load (below, after the last of them) names one: an entry point takes one snapshot and hands
+// it to conv_route / eval_route.
+static Policy g_select_n{0};                                            // conv_select.h ConvPolicy::select_n
+static Policy g_halo_force{-1}, g_pipe_force{-1}, g_direct_force{-1}, g_hpipe_force{-1};   // conv_*.h: the planners' rules
 
 extern "C" int ym_conv_set_select_batch(int n) {
     // kernel selection as if the batch held n images (0: the real batch); returns the previous setting
@@ -1158,14 +1152,90 @@ extern "C" int ym_conv_set_hpipe(int mode) {
     return g_hpipe_force.set(mode < -1 || mode > 2 ? -1 : mode);
 }
 
+// ------------------------------------------------------------------ kernel selection
+// The kernel of d's forward (dir 0) or data gradient (1) under pol, decided in one place.  The cascade, first hit
+// wins: direct register-weight kernel (conv_direct.hip) -> halo-staged pipelined 3x3 (conv_hpipe.hip) -> persistent
+// pipelined implicit GEMM (conv_pipe.hip) -> halo-staged 3x3 (conv_halo.hip) -> this file's 2-stage implicit GEMM.
+struct RouteOpts {
+    bool has_bias;       // the direct and halo-pipelined kernels have no bias term: a conv with bias skips them
+    bool inference;      // a forward without BatchNorm statistics: the direct kernel's lower threshold (direct_plan)
+};
+
+struct ConvRoute {
+    int algo;            // ym_conv_algo: 3 direct, 4 halo-pipelined, 2 pipelined GEMM, 1 halo, 0 2-stage GEMM
+    DirectPlan direct;   // the plan algo names (the others are not valid)
+    HPipePlan hpipe;
+    PipePlan pipe;
+    HaloPlan halo;
+    Tile tile;           // algo 0
+    int rows;            // forward: rows of the BN statistics partials the launch writes
+    int id;              // ym_conv_kernel: algo x 1000 + template instance
+};
+
+static ConvRoute conv_route(const ym_conv_desc* d, int dir, const ConvPolicy& pol, RouteOpts o) {
+    ConvRoute r{};
+    if (!o.has_bias && (r.direct = direct_plan(d, dir, pol, o.inference)).ok) {
+        r.algo = 3; r.rows = r.direct.grid; r.id = 3000 + r.direct.variant;
+    } else if (!o.has_bias && (r.hpipe = hpipe_plan(d, dir, pol)).ok) {
+        r.algo = 4; r.rows = r.hpipe.rows; r.id = 4000 + r.hpipe.cfg;
+    } else if ((r.pipe = pipe_plan(d, dir, pol)).ok) {
+        r.algo = 2; r.rows = r.pipe.rows; r.id = 2000 + r.pipe.cfg;
+    } else if ((r.halo = halo_plan(d, dir, pol)).ok) {
+        r.algo = 1; r.rows = r.halo.gx; r.id = 1000 + 100 * r.halo.cfg + std::min(r.halo.TW, 99);
+    } else {
+        // the tile for the selection batch's pixels (of the largest parity class), the rows for the real batch's
+        const ConvSide s = side(d, dir);
+        const int os = std::max(s.os, 1);               // (a descriptor is not validated here)
+        r.tile = pick_tile(pol.select_n(d) * ((s.OH + os - 1) / os) * ((s.OW + os - 1) / os), os == 2 ? 4 : 1, s.nout);
+        if (!dir) r.rows = gemm_stat_rows(int64_t(d->n) * s.OH * s.OW, r.tile, s.nout);
+        r.id = r.tile.bn;
+    }
+    return r;
+}
+
+// launches route r; a: the operands, and the 2-stage GEMM's arguments (algo 0).  fold: the BatchNorm finalize as the
+// launch's tail (ym_conv_fwd_bn: the pipelined, halo-staged and 2-stage GEMM forwards with statistics) or null
+static int route_launch(const ConvRoute& r, const ym_conv_desc* d, int dir, GemmArgs a, const ym_bn_fold* fold,
+                        hipStream_t st) {
+    switch (r.algo) {
+        case 3: direct_launch(r.direct, d, dir, a.x, a.w, a.y, a.st_sum, a.st_sq, st); break;
+        case 4: hpipe_launch(r.hpipe, d, dir, a.x, a.w, a.y, a.st_sum, a.st_sq, st); break;
+        case 2: pipe_launch(r.pipe, d, dir, a.x, a.w, a.y, a.bias, a.st_sum, a.st_sq, st, fold); break;
+        case 1: halo_launch(r.halo, d, dir, a.x, a.w, a.y, a.bias, a.st_sum, a.st_sq, st, fold); break;
+        default:
+            if (a.st_sum) a.fold = bn_fold_args(fold);
+            if (dir) launch_tile<MODE_DGRAD>(a, r.tile, 4096, st);
+            else launch_tile<MODE_FWD>(a, r.tile, FWD_STAT_BLOCKS, st);
+    }
+    static const char* const what[2][5] = {
+        {"ym_conv_fwd", "ym_conv_fwd (halo)", "ym_conv_fwd (pipe)", "ym_conv_fwd (direct)", "ym_conv_fwd (hpipe)"},
+        {"ym_conv_dgrad", "ym_conv_dgrad (halo)", "ym_conv_dgrad (pipe)", "ym_conv_dgrad (direct)",
+         "ym_conv_dgrad (hpipe)"}};
+    YM_LAUNCH_CHECK(what[dir][r.algo]);
+    return YM_OK;
+}
+
+// the 2-stage GEMM's view of d's forward (dir 0) or data gradient (1); the caller adds the operands and epilogue
+static GemmArgs gemm_args(const ym_conv_desc* d, int dir) {
+    const ConvSide s = side(d, dir);
+    GemmArgs a{};
+    a.x_bs = s.in_bs; a.x_ld = s.in_ld;
+    a.y_bs = s.out_bs; a.y_ld = s.out_ld;
+    a.GH = s.GH; a.GW = s.GW; a.Kin = s.kin;
+    a.OH = s.OH; a.OW = s.OW; a.Nout = s.nout;
+    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad;
+    a.M = int64_t(d->n) * s.OH * s.OW;
+    a.out_f32 = dir ? 0 : d->out_f32; a.accumulate = d->accumulate;
+    a.N = d->n;
+    a.ostep = s.os;      // stride-2 data gradient: one launch over the 4 output parity classes, each with its valid taps
+    return a;
+}
+
 extern "C" int ym_conv_algo(const ym_conv_desc* d, int dgrad) {
     // 4: halo-staged pipelined 3x3 kernel (conv_hpipe.hip), 3: direct register-weight kernel
     // (conv_direct.hip), 2: persistent pipelined implicit GEMM (conv_pipe.hip), 1: halo-staged 3x3 kernel
     // (conv_halo.hip), 0: 2-stage implicit GEMM
-    if (d && direct_plan(d, dgrad ? 1 : 0).ok) return 3;
-    if (d && hpipe_plan(d, dgrad ? 1 : 0).ok) return 4;
-    if (d && pipe_plan(d, dgrad ? 1 : 0).ok) return 2;
-    return d && halo_plan(d, dgrad ? 1 : 0).ok ? 1 : 0;
+    return d ? conv_route(d, dgrad ? 1 : 0, ConvPolicy::load(), {}).algo : 0;
 }
 
 extern "C" int ym_conv_kernel(const ym_conv_desc* d, int dir, char* name, int name_len) {
@@ -1179,29 +1249,17 @@ extern "C" int ym_conv_kernel(const ym_conv_desc* d, int dir, char* name, int na
     } else if (dir == 2) {
         id = wgrad_kernel(d, buf, sizeof buf);
     } else {
-        const DirectPlan dp = direct_plan(d, dir);
-        const HPipePlan hq = hpipe_plan(d, dir);
-        const PipePlan pp = pipe_plan(d, dir);
-        const HaloPlan hp = halo_plan(d, dir);
-        if (dp.ok) {
-            id = 3000 + dp.variant;
-            snprintf(buf, sizeof buf, "direct v%d", dp.variant);
-        } else if (hq.ok) {
-            id = 4000 + hq.cfg;
-            snprintf(buf, sizeof buf, "hpipe %s", hq.cfg == 0 ? "16x16px x 128" : hq.cfg == 1 ? "16x16px x 64" : "16x16px x 64 wres");
-        } else if (pp.ok) {
-            id = 2000 + pp.cfg;
-            static const char* const pipe_names[] = {"256x128", "256x64", "256x128 8w"};
-            snprintf(buf, sizeof buf, "pipe %s", pipe_names[pp.cfg]);
-        } else if (hp.ok) {
-            id = 1000 + 100 * hp.cfg + std::min(hp.TW, 99);
-            snprintf(buf, sizeof buf, "halo %s %dx%d", hp.cfg == 0 ? "C8" : "C4", hp.TH, hp.TW);
-        } else {
-            const int os = dir ? d->stride : 1;
-            const int OH = dir ? d->h : d->oh, OW = dir ? d->w : d->ow, nout = dir ? d->cin : d->cout;
-            const Tile t = pick_tile(select_n(d) * ((OH + os - 1) / os) * ((OW + os - 1) / os), os == 2 ? 4 : 1, nout);
-            id = t.bn;
-            snprintf(buf, sizeof buf, "gemm %dx%d%s", t.bm, t.bn, os == 2 ? " 4-class" : "");
+        const ConvRoute r = conv_route(d, dir, ConvPolicy::load(), {});
+        static const char* const hpipe_names[] = {"16x16px x 128", "16x16px x 64", "16x16px x 64 wres"};
+        static const char* const pipe_names[] = {"256x128", "256x64", "256x128 8w"};
+        id = r.id;
+        switch (r.algo) {
+            case 3: snprintf(buf, sizeof buf, "direct v%d", r.direct.variant); break;
+            case 4: snprintf(buf, sizeof buf, "hpipe %s", hpipe_names[r.hpipe.cfg]); break;
+            case 2: snprintf(buf, sizeof buf, "pipe %s", pipe_names[r.pipe.cfg]); break;
+            case 1: snprintf(buf, sizeof buf, "halo %s %dx%d", r.halo.cfg == 0 ? "C8" : "C4", r.halo.TH, r.halo.TW); break;
+            default:
+                snprintf(buf, sizeof buf, "gemm %dx%d%s", r.tile.bm, r.tile.bn, dir && d->stride == 2 ? " 4-class" : "");
         }
     }
     if (name && name_len > 0) snprintf(name, size_t(name_len), "%s", buf);
@@ -1209,25 +1267,21 @@ extern "C" int ym_conv_kernel(const ym_conv_desc* d, int dir, char* name, int na
 }
 
 extern "C" int ym_conv_fwd_stat_rows(const ym_conv_desc* d) {
-    // rows of the BN statistics partials ym_conv_fwd writes for this conv (halo or implicit-GEMM grid)
-    if (!d) return 0;
-    const DirectPlan dp = direct_plan(d, 0);
-    if (dp.ok) return dp.grid;
-    const HPipePlan hq = hpipe_plan(d, 0);
-    if (hq.ok) return hq.rows;
-    const PipePlan pp = pipe_plan(d, 0);
-    if (pp.ok) return pp.rows;
-    const HaloPlan hp = halo_plan(d, 0);
-    if (hp.ok) return hp.gx;
-    return gemm_stat_rows(int64_t(d->n) * d->oh * d->ow, select_n(d) * d->oh * d->ow, d->cout);
+    // rows of the BN statistics partials ym_conv_fwd writes for this conv (the grid of the kernel it routes to)
+    return d ? conv_route(d, 0, ConvPolicy::load(), {}).rows : 0;
 }
 
 // ym_conv_fwd_bn's fold policy (ym_conv_set_fold): -1 default (on), 0 off, 1 on
 static Policy g_fold_mode{-1};
 
-// fold: the BatchNorm finalize as the pipelined kernel's tail (ym_conv_fwd_bn), null elsewhere
+// ym_conv_fwd_bn folds the finalize into the launch's tail: the pipelined, halo-staged and 2-stage GEMM forwards
+// (bias-free, with statistics) have one; the direct and halo-pipelined forwards run conv + ym_bn_finalize
+static bool fold_fused(const ConvPolicy& pol, const ConvRoute& r) { return pol.fold != 0 && r.algo != 3 && r.algo != 4; }
+
+// fold: ym_conv_fwd_bn's BatchNorm, finalized in the launch where fold_fused, null elsewhere; taken: the route launched
 static int conv_fwd_impl(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, const float* bias,
-                         float* stat_sum, float* stat_sq, void* stream, const ym_bn_fold* fold = nullptr) {
+                         float* stat_sum, float* stat_sq, void* stream, const ConvPolicy& pol,
+                         const ym_bn_fold* fold = nullptr, ConvRoute* taken = nullptr) {
     YM_CHECK_ARG(d && x && w && y, "ym_conv_fwd: null argument");
     YM_CHECK_ARG(d->cin % 8 == 0, "ym_conv_fwd: Cin %% 8 != 0 (Cin=%d)", d->cin);
     YM_CHECK_ARG(d->k >= 1 && d->k <= 3, "ym_conv_fwd: kernel size %d unsupported (1..3)", d->k);
@@ -1237,66 +1291,31 @@ static int conv_fwd_impl(const ym_conv_desc* d, const uint16_t* x, const uint16_
     // the statistics row count (ym_conv_fwd_stat_rows) describes the bias-free forward of a Conv block
     YM_CHECK_ARG(!(bias && stat_sum), "ym_conv_fwd: BN statistics of a conv with bias are not supported");
     YM_CHECK_ARG(!(d->accumulate && d->out_f32 == 2), "ym_conv_fwd: accumulate into an fp16 output is not supported");
-    GemmArgs a{};
-    a.x = x; a.x_bs = d->x_bs; a.x_ld = d->x_ld;
-    a.w = w;
-    a.y = y; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
+    GemmArgs a = gemm_args(d, 0);
+    a.x = x; a.w = w; a.y = y;
     a.bias = bias; a.st_sum = stat_sum; a.st_sq = stat_sq;
-    a.GH = d->h; a.GW = d->w; a.Kin = d->cin;
-    a.OH = d->oh; a.OW = d->ow; a.Nout = d->cout;
-    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad;
-    a.M = int64_t(d->n) * d->oh * d->ow;
-    a.out_f32 = d->out_f32; a.accumulate = d->accumulate;
-    a.N = d->n;
-    a.ostep = 1;
     // fp16 z: the register-transposed epilogue with 16-B row stores (round 4; fp32 / bias outputs: fragment stores)
     a.ep_lds = d->out_f32 == 2 && !bias && d->y_ld % 8 == 0 && d->y_bs % 8 == 0 &&
                int64_t(d->n) * d->y_bs * 2 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(y) % 16 == 0;
+    const ConvRoute r = conv_route(d, 0, pol, {bias != nullptr, stat_sum == nullptr});
+    if (taken) *taken = r;
     if (a.M == 0) return YM_OK;
-    // the direct and halo-pipelined kernels have no bias term: a conv with bias takes the kernels below
-    const DirectPlan dp = bias ? DirectPlan{} : direct_plan(d, 0, stat_sum == nullptr);
-    if (dp.ok) {
-        direct_launch(dp, d, 0, x, w, y, stat_sum, stat_sq, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_fwd (direct)");
-        return YM_OK;
-    }
-    YM_CHECK_ARG(a.M < (int64_t(1) << 31), "ym_conv_fwd: too many pixels");
-    const HPipePlan hq = bias ? HPipePlan{} : hpipe_plan(d, 0);
-    if (hq.ok) {
-        hpipe_launch(hq, d, 0, x, w, y, stat_sum, stat_sq, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_fwd (hpipe)");
-        return YM_OK;
-    }
-    YM_CHECK_ARG(offsets_fit(d->x_bs, int64_t(d->oh) * d->ow), "ym_conv_fwd: input image stride too large");
-    const PipePlan pp = pipe_plan(d, 0);
-    if (pp.ok) {
-        pipe_launch(pp, d, 0, x, w, y, bias, stat_sum, stat_sq, as_stream(stream), fold);
-        YM_LAUNCH_CHECK("ym_conv_fwd (pipe)");
-        return YM_OK;
-    }
-    const HaloPlan hp = halo_plan(d, 0);
-    if (hp.ok) {
-        halo_launch(hp, d, 0, x, w, y, bias, stat_sum, stat_sq, as_stream(stream), fold);
-        YM_LAUNCH_CHECK("ym_conv_fwd (halo)");
-        return YM_OK;
-    }
-    if (stat_sum) a.fold = bn_fold_args(fold);
-    pick_and_launch(a, MODE_FWD, FWD_STAT_BLOCKS, select_n(d), as_stream(stream));
-    YM_LAUNCH_CHECK("ym_conv_fwd");
-    return YM_OK;
+    // the 32-bit pixel indices and buffer offsets of the kernels after the direct / the halo-pipelined one
+    YM_CHECK_ARG(r.algo == 3 || a.M < (int64_t(1) << 31), "ym_conv_fwd: too many pixels");
+    YM_CHECK_ARG(r.algo == 3 || r.algo == 4 || offsets_fit(d->x_bs, int64_t(d->oh) * d->ow),
+                 "ym_conv_fwd: input image stride too large");
+    return route_launch(r, d, 0, a, fold && fold_fused(pol, r) ? fold : nullptr, as_stream(stream));
 }
 
 extern "C" int ym_conv_fwd(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, const float* bias,
                            float* stat_sum, float* stat_sq, void* stream) {
-    return conv_fwd_impl(d, x, w, y, bias, stat_sum, stat_sq, stream);
+    return conv_fwd_impl(d, x, w, y, bias, stat_sum, stat_sq, stream, ConvPolicy::load());
 }
 
 extern "C" int ym_conv_fwd_bn_fused(const ym_conv_desc* d) {
-    // the pipelined, halo-staged and 2-stage GEMM forwards (bias-free, with statistics) fold the finalize into
-    // their tail; the direct and halo-pipelined forwards run conv + ym_bn_finalize
-    if (!d || g_fold_mode == 0) return 0;
-    if (direct_plan(d, 0).ok || hpipe_plan(d, 0).ok) return 0;
-    return 1;
+    if (!d) return 0;
+    const ConvPolicy pol = ConvPolicy::load();
+    return fold_fused(pol, conv_route(d, 0, pol, {})) ? 1 : 0;
 }
 
 extern "C" int ym_conv_fwd_bn(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, float* stat_sum,
@@ -1306,10 +1325,12 @@ extern "C" int ym_conv_fwd_bn(const ym_conv_desc* d, const uint16_t* x, const ui
                  "ym_conv_fwd_bn: null BatchNorm argument");
     YM_CHECK_ARG(bn->count > 0, "ym_conv_fwd_bn: count must be > 0");
     YM_CHECK_ARG(d->cout <= 2048, "ym_conv_fwd_bn: Cout=%d > 2048", d->cout);
-    if (ym_conv_fwd_bn_fused(d)) return conv_fwd_impl(d, x, w, y, nullptr, stat_sum, stat_sq, stream, bn);
-    const int r = conv_fwd_impl(d, x, w, y, nullptr, stat_sum, stat_sq, stream);
-    if (r != YM_OK) return r;
-    return ym_bn_finalize(stat_sum, stat_sq, ym_conv_fwd_stat_rows(d), d->cout, bn->count, bn->gamma, bn->beta,
+    const ConvPolicy pol = ConvPolicy::load();
+    ConvRoute r{};
+    const int st = conv_fwd_impl(d, x, w, y, nullptr, stat_sum, stat_sq, stream, pol, bn, &r);
+    if (st != YM_OK || fold_fused(pol, r)) return st;
+    // no fold tail: finalize the rows the route just launched wrote
+    return ym_bn_finalize(stat_sum, stat_sq, r.rows, d->cout, bn->count, bn->gamma, bn->beta,
                           bn->running_mean, bn->running_var, bn->num_batches_tracked, bn->momentum, bn->eps,
                           bn->scale, bn->shift, bn->mean, bn->rstd, bn->workspace, stream);
 }
@@ -1361,30 +1382,6 @@ extern "C" int ym_conv_set_eval_gemm_tiles(int max_tiles) {
     return g_eval_gemm_tiles.set(max_tiles < 0 ? 0 : max_tiles);
 }
 
-static int64_t eval_tiles(const ym_conv_desc* d) {
-    const int64_t M = int64_t(d->n) * d->oh * d->ow;
-    return ((M + 127) / 128) * ((d->cout + 63) / 64);
-}
-
-static bool eval_gemm_fits(const ym_conv_desc* d) {
-    const int64_t M = int64_t(d->n) * d->oh * d->ow;
-    return M < (int64_t(1) << 31) && offsets_fit(d->x_bs, int64_t(d->oh) * d->ow);
-}
-
-// K slices of d's eval forward (1: no split); d passed ym_conv_fwd_eval_ok's layout checks
-static int eval_ks(const ym_conv_desc* d) {
-    if (g_eval_split == 0 || !eval_gemm_fits(d)) return 1;
-    const int64_t M = int64_t(d->n) * d->oh * d->ow;
-    const int64_t tiles = ((M + 127) / 128) * ((d->cout + 63) / 64);
-    // K stages of the instance ym_conv_fwd_eval launches: the narrow (<= 32-channel) 128 x 32 tile always runs
-    // 64-deep stages, the 128 x 64 one 32-deep under eval cfg 0
-    const int KB = (g_eval_narrow && d->cout <= 32) || g_eval_cfg != 0 ? 64 : 32;
-    const int nk = d->k * d->k * ((d->cin + KB - 1) / KB);
-    if (tiles > g_eval_split || nk < g_eval_split_nk) return 1;
-    const int64_t ks = std::min<int64_t>(std::min<int64_t>(nk / 4, std::max<int64_t>(1, 256 / tiles)), 16);
-    return ks >= 2 && M * (d->cout / 8) < (int64_t(1) << 31) ? int(ks) : 1;
-}
-
 // the pipelined forward's eval instance for layers of >= 256 tiles (ym_conv_set_eval_pipe; 0: those layers run
 // ym_conv_fwd + ym_bn_apply)
 static Policy g_eval_pipe{1};
@@ -1404,42 +1401,84 @@ extern "C" int ym_conv_set_eval_route(int mask) {
     return g_eval_route.set(mask < 0 ? 0 : (mask & 3));
 }
 
-static bool eval_layout_ok(const ym_conv_desc* d) {
-    if (!d || d->cin % 8 || d->cout % 8 || d->k < 1 || d->k > 3 || d->out_f32 != 2 || d->accumulate) return false;
-    if (d->x_ld % 8 || d->x_bs % 8 || d->y_ld % 8 || d->y_bs % 8) return false;
-    if (int64_t(d->n) * d->y_bs * 2 >= (int64_t(1) << 31)) return false;
-    if (direct_plan(d, 0, true).ok) return false;                    // no eval epilogue there
-    if (hpipe_plan(d, 0).ok && !((g_eval_route & 2) && eval_gemm_fits(d))) return false;
-    const PipePlan pp = pipe_plan(d, 0);
-    return !pp.ok || (g_eval_pipe && pipe_eval_ok(pp, d));          // the pipelined forward's eval instance
+ConvPolicy ConvPolicy::load() {
+    ConvPolicy p;
+    p.select_batch = g_select_n;
+    p.halo = g_halo_force; p.pipe = g_pipe_force; p.direct = g_direct_force; p.hpipe = g_hpipe_force;
+    p.fold = g_fold_mode;
+    p.eval_cfg = g_eval_cfg; p.eval_narrow = g_eval_narrow;
+    p.eval_split = g_eval_split; p.eval_split_nk = g_eval_split_nk; p.eval_gemm_tiles = g_eval_gemm_tiles;
+    p.eval_pipe = g_eval_pipe; p.eval_route = g_eval_route;
+    return p;
 }
 
-// the eval forward runs the halo kernel's eval instance (not the GEMM) for d
-static bool eval_halo(const ym_conv_desc* d, const HaloPlan& hp) {
-    return hp.ok && hp.cfg == 1 && !(eval_tiles(d) <= g_eval_gemm_tiles && eval_gemm_fits(d));
+enum { EVAL_GEMM = 0, EVAL_HALO = 1, EVAL_PIPE = 2 };
+constexpr int EVAL_GEMM_NARROW = 3;     // EvalRoute.gemm: the 128 x 32 tile (0..2: the 128 x 64 tile under that eval cfg)
+
+// the eval decision for d under pol, made once: whether d is an eval-epilogue case, what it launches and the K-split
+struct EvalRoute {
+    int ok;              // ym_conv_fwd_eval_ok
+    int kind;            // what one launch runs: the pipelined forward's eval instance, the halo C4 one or the GEMM's
+    PipePlan pipe;       // EVAL_PIPE
+    HaloPlan halo;       // EVAL_HALO
+    int gemm;            // the GEMM instance: EVAL_GEMM_NARROW or the eval cfg.  Outputs of <= 32 channels: the 128 x 32
+                         // tile on 4 waves along the pixels (1 x 4: 32 channels per wave, the register epilogue's
+                         // minimum) instead of half-masking the 128 x 64 tile (ym_conv_set_eval_narrow)
+    int ks;              // K slices (1: no split) the GEMM runs when the caller gives a workspace of bytes — then in
+    size_t bytes;        // place of the halo instance too; without the workspace, kind in one launch
+};
+
+static EvalRoute eval_route(const ym_conv_desc* d, const ConvPolicy& pol) {
+    EvalRoute r{};
+    r.ks = 1;
+    if (!d || d->cin % 8 || d->cout % 8 || d->k < 1 || d->k > 3 || d->out_f32 != 2 || d->accumulate) return r;
+    if (d->x_ld % 8 || d->x_bs % 8 || d->y_ld % 8 || d->y_bs % 8) return r;
+    if (int64_t(d->n) * d->y_bs * 2 >= (int64_t(1) << 31)) return r;
+    const int64_t M = int64_t(d->n) * d->oh * d->ow;
+    const int64_t tiles = ((M + 127) / 128) * ((d->cout + 63) / 64);
+    const bool gemm_fits = M < (int64_t(1) << 31) && offsets_fit(d->x_bs, int64_t(d->oh) * d->ow);
+    if (direct_plan(d, 0, pol, true).ok) return r;                    // no eval epilogue there
+    if (hpipe_plan(d, 0, pol).ok && !((pol.eval_route & 2) && gemm_fits)) return r;
+    r.pipe = pipe_plan(d, 0, pol);
+    if (r.pipe.ok && !(pol.eval_pipe && pipe_eval_ok(r.pipe, d))) return r;   // the pipelined forward's eval instance
+    // K slices: the narrow (<= 32-channel) 128 x 32 tile always runs 64-deep stages, the 128 x 64 one 32-deep under
+    // eval cfg 0
+    r.gemm = pol.eval_narrow && d->cout <= 32 ? EVAL_GEMM_NARROW : pol.eval_cfg;
+    const int KB = r.gemm == 0 ? 32 : 64;
+    const int nk = d->k * d->k * ((d->cin + KB - 1) / KB);
+    if (pol.eval_split != 0 && gemm_fits && tiles <= pol.eval_split && nk >= pol.eval_split_nk) {
+        const int64_t ks = std::min<int64_t>(std::min<int64_t>(nk / 4, std::max<int64_t>(1, 256 / tiles)), 16);
+        if (ks >= 2 && M * (d->cout / 8) < (int64_t(1) << 31)) r.ks = int(ks);
+    }
+    r.bytes = r.ks > 1 ? size_t(r.ks) * size_t(M) * size_t(d->cout) * sizeof(float) : 0;
+    if (r.pipe.ok) {                              // large maps (>= 256 tiles)
+        r.kind = EVAL_PIPE;
+        r.ok = 1;
+        return r;
+    }
+    // small grids take the GEMM where the halo kernel would run (ym_conv_set_eval_gemm_tiles)
+    const bool small = tiles <= pol.eval_gemm_tiles && gemm_fits;
+    r.halo = halo_plan(d, 0, pol);
+    r.kind = r.halo.ok && r.halo.cfg == 1 && !small ? EVAL_HALO : EVAL_GEMM;
+    if (r.ks > 1 || small) r.ok = 1;
+    else if (r.halo.ok) r.ok = r.halo.cfg == 1 || ((pol.eval_route & 1) && gemm_fits);
+    else r.ok = gemm_fits;
+    return r;
 }
 
-extern "C" int ym_conv_fwd_eval_ok(const ym_conv_desc* d) {
-    if (!eval_layout_ok(d)) return 0;
-    if (pipe_plan(d, 0).ok) return 1;
-    if (eval_ks(d) > 1 || (eval_tiles(d) <= g_eval_gemm_tiles && eval_gemm_fits(d))) return 1;
-    const HaloPlan hp = halo_plan(d, 0);
-    if (hp.ok) return hp.cfg == 1 ? 1 : ((g_eval_route & 1) && eval_gemm_fits(d) ? 1 : 0);
-    return eval_gemm_fits(d) ? 1 : 0;
-}
+extern "C" int ym_conv_fwd_eval_ok(const ym_conv_desc* d) { return eval_route(d, ConvPolicy::load()).ok; }
 
 extern "C" size_t ym_conv_fwd_eval_workspace_size(const ym_conv_desc* d) {
     // bytes of the fp32 slice partials ym_conv_fwd_eval's K-split takes for d (0: one launch, no workspace)
-    if (!eval_layout_ok(d)) return 0;
-    const int ks = eval_ks(d);
-    return ks > 1 ? size_t(ks) * size_t(int64_t(d->n) * d->oh * d->ow) * size_t(d->cout) * sizeof(float) : 0;
+    return eval_route(d, ConvPolicy::load()).bytes;
 }
 
 extern "C" int ym_conv_fwd_eval(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, const float* scale,
                                 const float* shift, int act, const uint16_t* res, int64_t r_bs, int64_t r_ld,
                                 uint16_t* y, void* workspace, size_t workspace_bytes, void* stream) {
     YM_CHECK_ARG(d && x && w && scale && shift && y, "ym_conv_fwd_eval: null argument");
-    YM_CHECK_ARG(ym_conv_fwd_eval_ok(d), "ym_conv_fwd_eval: not an eval-epilogue case (ym_conv_fwd_eval_ok = 0)");
+    const EvalRoute r = eval_route(d, ConvPolicy::load());
+    YM_CHECK_ARG(r.ok, "ym_conv_fwd_eval: not an eval-epilogue case (ym_conv_fwd_eval_ok = 0)");
     YM_CHECK_ARG(reinterpret_cast<uintptr_t>(y) % 16 == 0 && reinterpret_cast<uintptr_t>(res) % 8 == 0 &&
                  reinterpret_cast<uintptr_t>(scale) % 16 == 0 && reinterpret_cast<uintptr_t>(shift) % 16 == 0,
                  "ym_conv_fwd_eval: misaligned output / residual / coefficient pointer");
@@ -1447,47 +1486,36 @@ extern "C" int ym_conv_fwd_eval(const ym_conv_desc* d, const uint16_t* x, const 
                           int64_t(d->n) * r_bs * 2 < (int64_t(1) << 31)),
                  "ym_conv_fwd_eval: residual view strides");
     if (int64_t(d->n) * d->oh * d->ow == 0) return YM_OK;
-    // the K-split where it applies and the caller gave its workspace (null / too small: one launch)
-    const size_t need = ym_conv_fwd_eval_workspace_size(d);
-    const int ks = need && workspace && workspace_bytes >= need && reinterpret_cast<uintptr_t>(workspace) % 16 == 0
-                       ? eval_ks(d) : 1;
+    // the K-split where the route has one and the caller gave the workspace this route needs (null, misaligned or
+    // smaller — sized under another setting: one launch)
+    const int ks = r.ks > 1 && workspace && workspace_bytes >= r.bytes && reinterpret_cast<uintptr_t>(workspace) % 16 == 0
+                       ? r.ks : 1;
     EvalArgs ev{scale, shift, act, res, int64_t(d->n) * r_bs * 2, r_bs, r_ld};
     if (ks > 1) {
         ev.ks = ks;
         ev.part = static_cast<float*>(workspace);
     }
     hipStream_t st = as_stream(stream);
-    const PipePlan pp = pipe_plan(d, 0);
-    if (pp.ok) {                                  // large maps (>= 256 tiles): the pipelined forward's eval instance
-        YM_CHECK_ARG(pipe_launch_eval(pp, d, x, w, y, ev, st) == 0, "ym_conv_fwd_eval: pipelined launch refused");
+    if (r.kind == EVAL_PIPE) {
+        YM_CHECK_ARG(pipe_launch_eval(r.pipe, d, x, w, y, ev, st) == 0, "ym_conv_fwd_eval: pipelined launch refused");
         YM_LAUNCH_CHECK("ym_conv_fwd_eval (pipe)");
         return YM_OK;
     }
-    const HaloPlan hp = halo_plan(d, 0);
-    if (ks == 1 && eval_halo(d, hp)) {
-        YM_CHECK_ARG(halo_launch(hp, d, 0, x, w, y, nullptr, nullptr, nullptr, st, nullptr, &ev) == 0,
+    if (r.kind == EVAL_HALO && ks == 1) {
+        YM_CHECK_ARG(halo_launch(r.halo, d, 0, x, w, y, nullptr, nullptr, nullptr, st, nullptr, &ev) == 0,
                      "ym_conv_fwd_eval: halo launch refused");
         YM_LAUNCH_CHECK("ym_conv_fwd_eval (halo)");
         return YM_OK;
     }
-    GemmArgs a{};
-    a.x = x; a.x_bs = d->x_bs; a.x_ld = d->x_ld;
-    a.w = w;
-    a.y = y; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-    a.GH = d->h; a.GW = d->w; a.Kin = d->cin;
-    a.OH = d->oh; a.OW = d->ow; a.Nout = d->cout;
-    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad;
-    a.M = int64_t(d->n) * d->oh * d->ow;
-    a.out_f32 = 2;
-    a.N = d->n;
-    a.ostep = 1;
+    GemmArgs a = gemm_args(d, 0);
+    a.x = x; a.w = w; a.y = y;
     a.ep_lds = 1;
-    // outputs of <= 32 channels: the 128 x 32 tile on 4 waves along the pixels (1 x 4: 32 channels per wave, the
-    // register epilogue's minimum) instead of half-masking the 128 x 64 tile (ym_conv_set_eval_narrow)
-    if (g_eval_narrow && d->cout <= 32) launch_gemm<128, 32, 1, 4, 64, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev);
-    else if (g_eval_cfg == 0) launch_gemm<128, 64, 2, 2, 32, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev);
-    else if (g_eval_cfg == 1) launch_gemm<128, 64, 2, 2, 64, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev);
-    else launch_gemm<128, 64, 2, 2, 64, 4, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev);
+    switch (r.gemm) {
+        case EVAL_GEMM_NARROW: launch_gemm<128, 32, 1, 4, 64, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev); break;
+        case 0: launch_gemm<128, 64, 2, 2, 32, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev); break;
+        case 1: launch_gemm<128, 64, 2, 2, 64, 3, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev); break;
+        default: launch_gemm<128, 64, 2, 2, 64, 4, MODE_FWD, true>(a, FWD_STAT_BLOCKS, st, ev);
+    }
     if (ks > 1) {
         const int64_t threads = a.M * (d->cout / 8);
         hipLaunchKernelGGL(eval_fold_kernel, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, st, ev.part, ks, a.M,
@@ -1509,53 +1537,17 @@ extern "C" int ym_conv_dgrad(const ym_conv_desc* d, const uint16_t* dz, const ui
     YM_CHECK_ARG(d->cout % 8 == 0, "ym_conv_dgrad: Cout %% 8 != 0 (Cout=%d)", d->cout);
     YM_CHECK_ARG(d->y_ld % 8 == 0 && d->y_bs % 8 == 0, "ym_conv_dgrad: dz view not 16-byte aligned");
     YM_CHECK_ARG(d->x_ld % 4 == 0 && d->x_bs % 4 == 0, "ym_conv_dgrad: dx view not 8-byte aligned");
-    GemmArgs a{};
-    a.x = dz; a.x_bs = d->y_bs; a.x_ld = d->y_ld;
-    a.w = wt;
-    a.y = dx; a.y_bs = d->x_bs; a.y_ld = d->x_ld;
-    a.GH = d->oh; a.GW = d->ow; a.Kin = d->cout;
-    a.OH = d->h; a.OW = d->w; a.Nout = d->cin;
-    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad;
-    a.M = int64_t(d->n) * d->h * d->w;
-    a.accumulate = d->accumulate;
-    a.N = d->n;
-    // stride-2: one launch over the 4 output parity classes, each with only its valid taps
     YM_CHECK_ARG(d->k >= 1 && d->k <= 3, "ym_conv_dgrad: kernel size %d unsupported (1..3)", d->k);
     YM_CHECK_ARG(d->stride == 1 || d->stride == 2, "ym_conv_dgrad: stride %d unsupported (1, 2)", d->stride);
-    a.ostep = d->stride;
+    GemmArgs a = gemm_args(d, 1);
+    a.x = dz; a.w = wt; a.y = dx;
     a.ep_lds = int64_t(d->n) * d->x_bs * 2 < (int64_t(1) << 31) && d->x_ld % 8 == 0 && d->x_bs % 8 == 0 &&
                reinterpret_cast<uintptr_t>(dx) % 16 == 0;     // 16-B stores of whole 8-channel runs
     if (a.M == 0) return YM_OK;
     YM_CHECK_ARG(a.M < (int64_t(1) << 31), "ym_conv_dgrad: too many pixels");
     YM_CHECK_ARG(offsets_fit(d->y_bs, int64_t(d->h / d->stride) * (d->w / d->stride)),
                  "ym_conv_dgrad: gradient image stride too large");
-    const DirectPlan dp = direct_plan(d, 1);
-    if (dp.ok) {
-        direct_launch(dp, d, 1, dz, wt, dx, nullptr, nullptr, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_dgrad (direct)");
-        return YM_OK;
-    }
-    const HPipePlan hq = hpipe_plan(d, 1);
-    if (hq.ok) {
-        hpipe_launch(hq, d, 1, dz, wt, dx, nullptr, nullptr, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_dgrad (hpipe)");
-        return YM_OK;
-    }
-    const PipePlan pp = pipe_plan(d, 1);
-    if (pp.ok) {
-        pipe_launch(pp, d, 1, dz, wt, dx, nullptr, nullptr, nullptr, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_dgrad (pipe)");
-        return YM_OK;
-    }
-    const HaloPlan hp = halo_plan(d, 1);
-    if (hp.ok) {
-        halo_launch(hp, d, 1, dz, wt, dx, nullptr, nullptr, nullptr, as_stream(stream));
-        YM_LAUNCH_CHECK("ym_conv_dgrad (halo)");
-        return YM_OK;
-    }
-    pick_and_launch(a, MODE_DGRAD, 4096, select_n(d), as_stream(stream));
-    YM_LAUNCH_CHECK("ym_conv_dgrad");
-    return YM_OK;
+    return route_launch(conv_route(d, 1, ConvPolicy::load(), {}), d, 1, a, nullptr, as_stream(stream));
 }
 
 // channel pieces of a c-channel layer for the lane-group kernels (stem, depthwise): powers of two of 8-channel groups,

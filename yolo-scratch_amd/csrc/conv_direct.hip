@@ -29,8 +29,6 @@
 
 namespace ym {
 
-Policy g_direct_force{-1};
-
 namespace {
 
 struct DirArgs {
@@ -450,7 +448,7 @@ const Variant kVariants[] = {
 // and the bs64 step unchanged in sum, but it moves the 80x80 layers of the bs64 step to this kernel and the largest
 // of them (128 -> 128 3x3 s2, the bench line's probe) ran 0.174 -> 0.203 ms: kept at 1
 // (profiles/r05/direct_threshold_ab.txt)
-int direct_mode() { return g_direct_force >= 0 ? g_direct_force : 1; }
+constexpr int kDirectDefault = 1;
 
 // workgroups of variant i the whole chip holds at once (CUs x the kernel's occupancy), cached per device and
 // variant; the cache entries are atomics, so concurrent planners at worst compute the same value twice
@@ -474,26 +472,24 @@ int resident_blocks(int i) {
 
 }  // namespace
 
-DirectPlan direct_plan(const ym_conv_desc* d, int dgrad, bool inference) {
+DirectPlan direct_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol, bool inference) {
     DirectPlan p{};
-    int mode = direct_mode();
+    int mode = pol.direct >= 0 ? pol.direct : kDirectDefault;
     // the inference forward (no statistics): mode 3's threshold under the default policy (s@640 bs 8 / 32 +0-2 / +3-4 %,
     // profiles/r05/direct_threshold_ab.txt; the training step keeps 1 M: its 80x80 layers ran slower here)
-    if (inference && !dgrad && mode == 1 && g_direct_force < 0) mode = 3;
+    if (inference && !dgrad && pol.direct < 0) mode = 3;
     if (!d || mode == 0) return p;
     if (d->k != 1 && d->k != 3) return p;
     if (d->pad != d->k / 2 || (d->stride != 1 && d->stride != 2)) return p;
     if (dgrad && d->k == 1 && d->stride != 1) return p;
-    const int kin = dgrad ? d->cout : d->cin, nout = dgrad ? d->cin : d->cout;
+    const ConvSide s = side(d, dgrad);
+    const int kin = s.kin, nout = s.nout, OH = s.OH, OW = s.OW;
     if (kin % 32 || nout % 8) return p;
     if (!dgrad && d->out_f32 != 2) return p;          // z (fp16) of a Conv block only
-    const int64_t in_ld = dgrad ? d->y_ld : d->x_ld, in_bs = dgrad ? d->y_bs : d->x_bs;
-    const int64_t out_ld = dgrad ? d->x_ld : d->y_ld, out_bs = dgrad ? d->x_bs : d->y_bs;
-    if (in_ld % 8 || in_bs % 8 || out_ld % 4 || out_bs % 4) return p;
-    if (int64_t(d->n) * in_bs * 2 >= (int64_t(1) << 31) || int64_t(d->n) * out_bs * 2 >= (int64_t(1) << 31)) return p;
+    if (s.in_ld % 8 || s.in_bs % 8 || s.out_ld % 4 || s.out_bs % 4) return p;
+    if (int64_t(d->n) * s.in_bs * 2 >= (int64_t(1) << 31) || int64_t(d->n) * s.out_bs * 2 >= (int64_t(1) << 31)) return p;
     // high-resolution maps only (where the implicit GEMMs are latency-bound): >= 1 M output pixels
-    const int OH = dgrad ? d->h : d->oh, OW = dgrad ? d->w : d->ow;
-    const int64_t M = select_n(d) * OH * OW;
+    const int64_t M = pol.select_n(d) * OH * OW;
     if (mode == 1 && M < (int64_t(1) << 20)) return p;
     if (mode == 3 && M < 200000) return p;          // >= 200 k: the 160x160 stage from 8 images up
     for (int i = 0; i < int(sizeof(kVariants) / sizeof(kVariants[0])); ++i) {
@@ -502,8 +498,7 @@ DirectPlan direct_plan(const ym_conv_desc* d, int dgrad, bool inference) {
         if (v.nt * 16 < nout || (v.nt - 1) * 16 >= nout) continue;
         p.ok = 1;
         p.variant = i;
-        const int os = dgrad ? d->stride : 1;
-        const int64_t OHc = (OH + os - 1) / os, OWc = (OW + os - 1) / os;
+        const int64_t OHc = (OH + s.os - 1) / s.os, OWc = (OW + s.os - 1) / s.os;
         const int64_t tpc = (int64_t(d->n) * OHc * OWc + 16 * v.tp - 1) / (16 * v.tp);
         // persistent: as many workgroups as the chip holds at once (1024 before: model.1 forward -12 %, its data
         // gradient -5.5 %, the other stem-stage layers -1..-10 %, profiles/r03/direct_grid_ab.txt)
@@ -518,17 +513,13 @@ int direct_launch(const DirectPlan& p, const ym_conv_desc* d, int dgrad, const u
                   void* y, float* st_sum, float* st_sq, hipStream_t st) {
     const Variant& v = kVariants[p.variant];
     DirArgs a{};
+    const ConvSide s = side(d, dgrad);
     a.x = x; a.w = w; a.y = y;
-    if (!dgrad) {
-        a.x_bs = d->x_bs; a.x_ld = d->x_ld; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-        a.GH = d->h; a.GW = d->w; a.OH = d->oh; a.OW = d->ow; a.Kin = d->cin; a.Nout = d->cout;
-        a.st_sum = st_sum; a.st_sq = st_sq;
-    } else {
-        a.x_bs = d->y_bs; a.x_ld = d->y_ld; a.y_bs = d->x_bs; a.y_ld = d->x_ld;
-        a.GH = d->oh; a.GW = d->ow; a.OH = d->h; a.OW = d->w; a.Kin = d->cout; a.Nout = d->cin;
-    }
+    a.x_bs = s.in_bs; a.x_ld = s.in_ld; a.y_bs = s.out_bs; a.y_ld = s.out_ld;
+    a.GH = s.GH; a.GW = s.GW; a.OH = s.OH; a.OW = s.OW; a.Kin = s.kin; a.Nout = s.nout;
+    if (!dgrad) { a.st_sum = st_sum; a.st_sq = st_sq; }
     a.N = d->n; a.pad = d->pad; a.accumulate = d->accumulate;
-    const int os = dgrad ? d->stride : 1;
+    const int os = s.os;
     a.OHc = (a.OH + os - 1) / os; a.OWc = (a.OW + os - 1) / os;   // (stride 2: quad rows / columns)
     a.tpc = (int64_t(a.N) * a.OHc * a.OWc + 16 * v.tp - 1) / (16 * v.tp);
     hipLaunchKernelGGL(v.fn, dim3(p.grid), dim3(256), 0, st, a);

@@ -1,7 +1,7 @@
 // Halo-staged 3x3 stride-1 convolution (conv_halo.hip): applicability plan + launch, used by
 // ym_conv_fwd / ym_conv_dgrad in conv.hip before they fall back to the implicit GEMM.
 #pragma once
-#include "common.h"
+#include "conv_select.h"
 
 namespace ym {
 
@@ -14,12 +14,10 @@ struct HaloPlan {
     int gx;              // grid x (= rows of the BN statistics partials)
 };
 
-// -1: default policy (3); 0 never; 1 wherever it applies; 2 maps <= 24 wide; 3 maps <= 48
+// pol.halo: -1 default policy (3); 0 never; 1 wherever it applies; 2 maps <= 24 wide; 3 maps <= 48
 // wide or <= 64 output channels (ym_conv_set_halo)
-extern Policy g_halo_force;
-
 // dgrad = 0: forward conv described by d; 1: its data gradient
-HaloPlan halo_plan(const ym_conv_desc* d, int dgrad);
+HaloPlan halo_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol);
 // fold: the BatchNorm finalize as the launch's tail (ym_conv_fwd_bn; forward with statistics only) or null
 // ev: the eval-mode Conv block epilogue (ym_conv_fwd_eval: forward, fp16 output view, no statistics) or null
 int halo_launch(const HaloPlan& p, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y,

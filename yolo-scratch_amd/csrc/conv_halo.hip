@@ -429,26 +429,21 @@ static bool pick_rect(int OH, int OW, int tp, int hpad, int& TH, int& TW) {
 
 }  // namespace
 
-Policy g_halo_force{-1};
-
-HaloPlan halo_plan(const ym_conv_desc* d, int dgrad) {
+HaloPlan halo_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol) {
     HaloPlan p{};
     // policy (ym_conv_set_halo): 0 never, 1 wherever it applies, 2 maps <= 24 wide (the 20x20 layers), 3 (the
     // default) maps <= 48 wide or <= 64 output channels — with the pipelined kernel taking the >= 128-channel
     // layers first, this rule measured 2953 vs 2940 img/s over rule 2 (s@640 bs64)
-    const int force = g_halo_force >= 0 ? g_halo_force : 3;
+    const int force = pol.halo >= 0 ? pol.halo : 3;
     if (force == 0) return p;
-    const int ow_ = dgrad ? d->w : d->ow, cout_ = dgrad ? d->cin : d->cout;
-    if (force == 2 && ow_ > 24) return p;
-    if (force == 3 && ow_ > 48 && cout_ > 64) return p;
+    const ConvSide s = side(d, dgrad);
+    const int cin = s.kin, cout = s.nout, OH = s.OH, OW = s.OW;
+    if (force == 2 && OW > 24) return p;
+    if (force == 3 && OW > 48 && cout > 64) return p;
     // 3x3, stride 1, pad 1, channels in whole 16-B chunks
-    const int cin = dgrad ? d->cout : d->cin, cout = dgrad ? d->cin : d->cout;
-    const int GH = dgrad ? d->oh : d->h, GW = dgrad ? d->ow : d->w;
-    const int OH = dgrad ? d->h : d->oh, OW = dgrad ? d->w : d->ow;
-    if (d->k != 3 || d->stride != 1 || d->pad != 1 || GH != OH || GW != OW) return p;
+    if (d->k != 3 || d->stride != 1 || d->pad != 1 || s.GH != OH || s.GW != OW) return p;
     if (cin % 8 != 0 || cout < 64) return p;
-    const int64_t xbs = dgrad ? d->y_bs : d->x_bs;
-    if (xbs * 2 >= (int64_t(1) << 31)) return p;
+    if (s.in_bs * 2 >= (int64_t(1) << 31)) return p;
     // C8 when it still gives one workgroup per CU, else C4
     for (int c = 0; c < 2; ++c) {
         const Cfg cf = c == 0 ? C8 : C4;
@@ -457,7 +452,7 @@ HaloPlan halo_plan(const ym_conv_desc* d, int dgrad) {
         const int RT = (OH + TH - 1) / TH, CT = (OW + TW - 1) / TW;
         const int64_t tiles = int64_t(d->n) * RT * CT;
         const int nco = (cout + cf.bn - 1) / cf.bn;
-        const int64_t sel_tiles = select_n(d) * RT * CT;
+        const int64_t sel_tiles = pol.select_n(d) * RT * CT;
         if (c == 0 && (sel_tiles * nco < 256 || cout <= 64)) continue;   // 128-channel tiles need >= 65 channels
         if (tiles >= (int64_t(1) << 30)) continue;
         p.ok = 1;
@@ -483,15 +478,10 @@ int halo_launch(const HaloPlan& p, const ym_conv_desc* d, int dgrad, const uint1
     a.bias = bias;
     a.st_sum = st_sum; a.st_sq = st_sq;
     a.N = d->n;
-    if (!dgrad) {
-        a.x_bs = d->x_bs; a.x_ld = d->x_ld; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-        a.GH = d->h; a.GW = d->w; a.Kin = d->cin; a.OH = d->oh; a.OW = d->ow; a.Nout = d->cout;
-        a.out_mode = d->out_f32;
-    } else {
-        a.x_bs = d->y_bs; a.x_ld = d->y_ld; a.y_bs = d->x_bs; a.y_ld = d->x_ld;
-        a.GH = d->oh; a.GW = d->ow; a.Kin = d->cout; a.OH = d->h; a.OW = d->w; a.Nout = d->cin;
-        a.out_mode = 0;
-    }
+    const ConvSide s = side(d, dgrad);
+    a.x_bs = s.in_bs; a.x_ld = s.in_ld; a.y_bs = s.out_bs; a.y_ld = s.out_ld;
+    a.GH = s.GH; a.GW = s.GW; a.Kin = s.kin; a.OH = s.OH; a.OW = s.OW; a.Nout = s.nout;
+    a.out_mode = dgrad ? 0 : d->out_f32;
     a.accumulate = d->accumulate;
     a.TH = p.TH; a.TW = p.TW; a.HWd = p.TW + 2; a.HP = (p.TH + 2) * (p.TW + 2);
     // 16-B epilogue stores of transposed pixel rows (round 2 through LDS: 64-ch 80x80 fwd 0.076 -> 0.070 ms, dgrad

@@ -1,7 +1,7 @@
 // Halo-staged persistent pipelined 3x3 stride-1 convolution (conv_hpipe.hip): applicability plan +
 // launch, used by ym_conv_fwd / ym_conv_dgrad in conv.hip ahead of the other conv kernels.
 #pragma once
-#include "common.h"
+#include "conv_select.h"
 
 namespace ym {
 
@@ -12,11 +12,9 @@ struct HPipePlan {
     int rows;        // rows of the BN statistics partials (= grid / channel tiles)
 };
 
-// selection policy (ym_conv_set_hpipe): -1 default (1); 0 never; 1 the weight-resident 64 -> 64 layers with >= 512 tiles;
+// pol.hpipe (ym_conv_set_hpipe): -1 default (1); 0 never; 1 the weight-resident 64 -> 64 layers with >= 512 tiles;
 // 2 every eligible layer
-extern Policy g_hpipe_force;
-
-HPipePlan hpipe_plan(const ym_conv_desc* d, int dgrad);
+HPipePlan hpipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol);
 int hpipe_launch(const HPipePlan& p, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y,
                  float* st_sum, float* st_sq, hipStream_t st);
 

@@ -34,8 +34,6 @@
 
 namespace ym {
 
-Policy g_hpipe_force{-1};
-
 namespace {
 
 constexpr int HF = 0;   // forward: fp16 x fp16
@@ -391,13 +389,14 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_hpipe_kernel(HArgs a) {
 
 }  // namespace
 
-HPipePlan hpipe_plan(const ym_conv_desc* d, int dgrad) {
+HPipePlan hpipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol) {
     HPipePlan p{};
-    const int mode = g_hpipe_force >= 0 ? g_hpipe_force : 1;
+    const int mode = pol.hpipe >= 0 ? pol.hpipe : 1;
     if (!d || mode == 0) return p;
     if (d->k != 3 || d->stride != 1 || d->pad != 1) return p;
     if (d->h != d->oh || d->w != d->ow || d->h % TS || d->w % TS) return p;
-    const int kin = dgrad ? d->cout : d->cin, nout = dgrad ? d->cin : d->cout;
+    const ConvSide s = side(d, dgrad);
+    const int kin = s.kin, nout = s.nout;
     // >= 128 output channels: the 64-channel tile (8 MFMAs per half step and wave) measured slower than
     // conv_halo.hip on the 64-channel 80x80 layers (0.080 vs 0.070 ms fwd, s@640 bs64)
     if (kin % 64 != 0 || nout % 8 != 0) return p;
@@ -405,15 +404,13 @@ HPipePlan hpipe_plan(const ym_conv_desc* d, int dgrad) {
     // dgrad 57 -> 53 us against conv_halo); other < 128-channel layers stay on conv_halo
     const bool wres = kin == 64 && nout == 64;
     if (nout < 128 && !wres) return p;
-    const int64_t in_ld = dgrad ? d->y_ld : d->x_ld, in_bs = dgrad ? d->y_bs : d->x_bs;
-    const int64_t out_ld = dgrad ? d->x_ld : d->y_ld, out_bs = dgrad ? d->x_bs : d->y_bs;
-    if (in_ld % 8 || in_bs % 8 || out_ld % 8 || out_bs % 8) return p;
+    if (s.in_ld % 8 || s.in_bs % 8 || s.out_ld % 8 || s.out_bs % 8) return p;
     if (!dgrad && d->out_f32 == 1) return p;                     // Detect's fp32 bias convs: conv.hip
-    if (int64_t(d->n) * in_bs * 2 >= (int64_t(1) << 31) || int64_t(d->n) * out_bs * 2 >= (int64_t(1) << 31)) return p;
+    if (int64_t(d->n) * s.in_bs * 2 >= (int64_t(1) << 31) || int64_t(d->n) * s.out_bs * 2 >= (int64_t(1) << 31)) return p;
     p.cfg = nout >= 128 ? 0 : (wres ? 2 : 1);
     const int bn = p.cfg == 0 ? 128 : 64;
     const int ntiles = (nout + bn - 1) / bn;
-    const int64_t tiles = select_n(d) * (d->h / TS) * (d->w / TS);
+    const int64_t tiles = pol.select_n(d) * (d->h / TS) * (d->w / TS);
     if (mode == 1 && tiles * ntiles < 512) return p;          // several tiles per CU (tail imbalance)
     // default: the weight-resident 64 -> 64 tile only — since round 4 the pipelined implicit GEMM (conv_pipe.hip)
     // runs the >= 128-output-channel 80x80 layers 9-12 % faster than the 128-channel halo tile (same-process
@@ -439,16 +436,11 @@ int hpipe_launch(const HPipePlan& p, const ym_conv_desc* d, int dgrad, const uin
     a.N = d->n;
     a.H = d->h;
     a.W = d->w;
-    if (!dgrad) {
-        a.x_bs = d->x_bs; a.x_ld = d->x_ld; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-        a.Kin = d->cin; a.Nout = d->cout;
-        a.out_f32 = d->out_f32;
-        a.st_sum = st_sum; a.st_sq = st_sq;
-    } else {
-        a.x_bs = d->y_bs; a.x_ld = d->y_ld; a.y_bs = d->x_bs; a.y_ld = d->x_ld;
-        a.Kin = d->cout; a.Nout = d->cin;
-        a.out_f32 = 0;
-    }
+    const ConvSide s = side(d, dgrad);
+    a.x_bs = s.in_bs; a.x_ld = s.in_ld; a.y_bs = s.out_bs; a.y_ld = s.out_ld;
+    a.Kin = s.kin; a.Nout = s.nout;
+    a.out_f32 = dgrad ? 0 : d->out_f32;
+    if (!dgrad) { a.st_sum = st_sum; a.st_sq = st_sq; }
     a.accumulate = d->accumulate;
     const int bn = p.cfg == 0 ? 128 : 64;
     a.ntiles = (a.Nout + bn - 1) / bn;
@@ -457,7 +449,7 @@ int hpipe_launch(const HPipePlan& p, const ym_conv_desc* d, int dgrad, const uin
     a.mt_total = a.N * a.tpi;
     if (p.cfg == 2) {
 #ifdef YM_EXPERIMENTS
-        if (g_pipe_order) {
+        if (pipe_order_exp()) {
             if (!dgrad) conv_hpipe_kernel<64, 1, 8, HF, true, 1><<<dim3(p.grid), dim3(512), 0, st>>>(a);
             else conv_hpipe_kernel<64, 1, 8, HD, true, 1><<<dim3(p.grid), dim3(512), 0, st>>>(a);
             return 0;

@@ -2,7 +2,7 @@
 // launch, used by ym_conv_fwd / ym_conv_dgrad in conv.hip ahead of the halo kernel and the
 // 2-stage implicit GEMM.
 #pragma once
-#include "common.h"
+#include "conv_select.h"
 
 namespace ym {
 
@@ -14,15 +14,14 @@ struct PipePlan {
     int rows;        // rows of the BN statistics partials (= grid / channel tiles)
 };
 
-// -1: default policy (3); 0 never; 1 layers of >= 1024 tiles, >= 128 channels; 2 >= 256
+// pol.pipe: -1 default policy (3); 0 never; 1 layers of >= 1024 tiles, >= 128 channels; 2 >= 256
 // tiles; 3 the wider rule of pipe_plan (ym_conv_set_pipe)
-extern Policy g_pipe_force;
 #ifdef YM_EXPERIMENTS
-extern Policy g_pipe_order;     // K-step issue order of the pipelined kernels (conv_pipe / conv_hpipe RO; measurement only)
+int pipe_order_exp();     // K-step issue order of the pipelined kernels (conv_pipe / conv_hpipe RO; measurement only)
 #endif
 
 // dgrad = 0: forward conv described by d; 1: its data gradient
-PipePlan pipe_plan(const ym_conv_desc* d, int dgrad);
+PipePlan pipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol);
 // fold: the BatchNorm finalize as the launch's tail (ym_conv_fwd_bn; forward with statistics only) or null
 int pipe_launch(const PipePlan& p, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y,
                 const float* bias, float* st_sum, float* st_sq, hipStream_t st, const ym_bn_fold* fold = nullptr);

@@ -40,7 +40,6 @@ namespace ym {
 // selection policy (ym_conv_set_pipe): -1 default (3); 0 never; 1 layers of >= 1024 tiles with >= 128
 // output channels, no stride-2 data gradient; 2 every eligible layer of >= 256 tiles; 3 (default) the
 // wider rule of pipe_plan (s@640 bs64 step: 2940 img/s vs 2902 for rule 1)
-Policy g_pipe_force{-1};
 // experiments (ym_pipe_set_exp, yolomi_experimental.h; tools/pipe_ab.py): 0 shipped; 1 the 8-wave 256 x 128 tile;
 // 10-13 ablations of the 16-wave tile (conv_pipe_kernel ABL 1, 2, 4, 8: wrong results by design); 20 the generic
 // (class-search) control path.  Built only into the measurement library (make exp: -DYM_EXPERIMENTS,
@@ -51,7 +50,7 @@ Policy g_pipe_force{-1};
 // RO: 1 pins every fragment read ahead of the MFMAs it covers, -3..+7 %)
 #ifdef YM_EXPERIMENTS
 Policy g_pipe_mfma{0};
-Policy g_pipe_order{0};   // also conv_hpipe.hip (conv_pipe.h)
+Policy g_pipe_order{0};   // also conv_hpipe.hip (pipe_order_exp)
 Policy g_pipe_loop{2};    // conv_pipe_kernel LP of the single-class path (2 shipped)
 Policy g_pipe_eval_loop{0};  // conv_pipe_kernel LP of the eval instance (0 shipped, 2 the nested loop)
 Policy g_pipe_taporder{-1};  // conv_pipe_kernel TO of the single-class forward: -1 the shipped rule (tap_inner), 0 / 1 forced
@@ -866,30 +865,27 @@ void launch_cfg(int mode, int cfg, const PipeArgs& a, int grid, hipStream_t st) 
 
 }  // namespace
 
-PipePlan pipe_plan(const ym_conv_desc* d, int dgrad) {
+PipePlan pipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol) {
     PipePlan p{};
-    const int mode = g_pipe_force >= 0 ? g_pipe_force : 3;
+    const int mode = pol.pipe >= 0 ? pol.pipe : 3;
     if (!d || mode == 0) return p;
-    const int kin = dgrad ? d->cout : d->cin, nout = dgrad ? d->cin : d->cout;
+    const ConvSide s = side(d, dgrad);
+    const int kin = s.kin, nout = s.nout, os = s.os, OH = s.OH, OW = s.OW;
     if (kin % 64 != 0 || nout % 8 != 0) return p;
     if (d->k != 3 && d->k != 1) return p;
     if (d->stride != 1 && d->stride != 2) return p;
     if (dgrad && d->k == 1 && d->stride == 2) return p;
-    const int64_t in_ld = dgrad ? d->y_ld : d->x_ld, in_bs = dgrad ? d->y_bs : d->x_bs;
-    const int64_t out_ld = dgrad ? d->x_ld : d->y_ld, out_bs = dgrad ? d->x_bs : d->y_bs;
-    if (in_ld % 8 || in_bs % 8 || out_ld % 4 || out_bs % 4) return p;
+    if (s.in_ld % 8 || s.in_bs % 8 || s.out_ld % 4 || s.out_bs % 4) return p;
     if (!dgrad && d->out_f32 == 1) return p;       // Detect's fp32 bias convs stay on conv.hip
-    const int os = dgrad ? d->stride : 1;
     // rule 1: only where it measured faster in isolation (tools/pipe_check.py): >= 128 output channels
     // (the 256 x 128 tile) and no stride-2 data gradient
     if (mode == 1 && (nout < 128 || os == 2)) return p;
     // 3: the wider rule (A/B runs): every 1x1, and 3x3 with >= 128 output channels or (forward) >= 128
     // input channels, at >= 256 tiles; never the stride-2 data gradient
     if (mode == 3 && (os == 2 || (d->k == 3 && nout < 128 && (dgrad || kin < 128)))) return p;
-    const int OH = dgrad ? d->h : d->oh, OW = dgrad ? d->w : d->ow;
     // split_pix: in-image pixel indices as exact floats, row estimates within one of the truth
     if (int64_t(OH) * OW >= (int64_t(1) << 24) || OH >= (1 << 16)) return p;
-    const int64_t M = select_n(d) * ((OH + os - 1) / os) * ((OW + os - 1) / os) * os * os;
+    const int64_t M = pol.select_n(d) * ((OH + os - 1) / os) * ((OW + os - 1) / os) * os * os;
     p.cfg = nout >= 128 ? 0 : 1;
     if (g_pipe_exp == 1 && nout >= 128) p.cfg = 2;
     const int bm = kCfg[p.cfg].bm, bn = kCfg[p.cfg].bn;
@@ -898,7 +894,7 @@ PipePlan pipe_plan(const ym_conv_desc* d, int dgrad) {
     // enough tiles to keep every CU busy for several tiles (tail imbalance), else conv.hip's kernels
     if (tiles < int64_t(mode >= 2 ? 256 : 1024)) return p;
     // 32-bit buffer offsets relative to a tile's first image
-    if (in_bs * 2 * (256 / std::max<int64_t>(int64_t(OH / os) * (OW / os), 1) + 2) >= (int64_t(1) << 31)) return p;
+    if (s.in_bs * 2 * (256 / std::max<int64_t>(int64_t(OH / os) * (OW / os), 1) + 2) >= (int64_t(1) << 31)) return p;
     int grid = 256;
     const int unit = 8 * ntiles;
     grid = (grid / unit) * unit;
@@ -910,6 +906,8 @@ PipePlan pipe_plan(const ym_conv_desc* d, int dgrad) {
 }
 
 #ifdef YM_EXPERIMENTS
+int pipe_order_exp() { return g_pipe_order; }
+
 extern "C" int ym_conv_set_pipe_order(int mode) {
     // K-step issue order of the pipelined kernel (conv_pipe_kernel RO: 0 default, 1 fragment reads pinned first)
     return g_pipe_order.set(mode < 0 || mode > 1 ? 0 : mode);
@@ -942,28 +940,25 @@ extern "C" int ym_pipe_set_exp(int v) {
 }
 #endif
 
+// operands, views and map geometry of d's forward (dgrad 0) or data gradient
+static void pipe_geometry(PipeArgs& a, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y) {
+    const ConvSide s = side(d, dgrad);
+    a.x = x; a.x_bs = s.in_bs; a.x_ld = s.in_ld;
+    a.y = y; a.y_bs = s.out_bs; a.y_ld = s.out_ld;
+    a.GH = s.GH; a.GW = s.GW; a.Kin = s.kin;
+    a.OH = s.OH; a.OW = s.OW; a.Nout = s.nout;
+    a.os = s.os;
+    a.w = w;
+    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad; a.N = d->n;
+}
+
 int pipe_launch(const PipePlan& p, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y,
                 const float* bias, float* st_sum, float* st_sq, hipStream_t st, const ym_bn_fold* fold) {
     PipeArgs a{};
     const int bm = kCfg[p.cfg].bm, bn = kCfg[p.cfg].bn;
-    if (!dgrad) {
-        a.x = x; a.x_bs = d->x_bs; a.x_ld = d->x_ld;
-        a.y = y; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-        a.GH = d->h; a.GW = d->w; a.Kin = d->cin;
-        a.OH = d->oh; a.OW = d->ow; a.Nout = d->cout;
-        a.os = 1;
-        a.out_f32 = d->out_f32;
-    } else {
-        a.x = x; a.x_bs = d->y_bs; a.x_ld = d->y_ld;
-        a.y = y; a.y_bs = d->x_bs; a.y_ld = d->x_ld;
-        a.GH = d->oh; a.GW = d->ow; a.Kin = d->cout;
-        a.OH = d->h; a.OW = d->w; a.Nout = d->cin;
-        a.os = d->stride;
-        a.out_f32 = 0;
-    }
-    a.w = w;
+    pipe_geometry(a, d, dgrad, x, w, y);
+    a.out_f32 = dgrad ? 0 : d->out_f32;
     a.bias = bias; a.st_sum = st_sum; a.st_sq = st_sq;
-    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad; a.N = d->n;
     a.accumulate = d->accumulate;
     a.ntiles = (a.Nout + bn - 1) / bn;
     a.ncls = a.os == 2 ? 4 : 1;
@@ -989,14 +984,8 @@ int pipe_launch_eval(const PipePlan& p, const ym_conv_desc* d, const uint16_t* x
                      const EvalArgs& e, hipStream_t st) {
     if (!pipe_eval_ok(p, d)) return 1;
     PipeArgs a{};
-    a.x = x; a.x_bs = d->x_bs; a.x_ld = d->x_ld;
-    a.y = y; a.y_bs = d->y_bs; a.y_ld = d->y_ld;
-    a.GH = d->h; a.GW = d->w; a.Kin = d->cin;
-    a.OH = d->oh; a.OW = d->ow; a.Nout = d->cout;
-    a.os = 1;
+    pipe_geometry(a, d, 0, x, w, y);
     a.out_f32 = 2;
-    a.w = w;
-    a.KH = d->k; a.KW = d->k; a.stride = d->stride; a.pad = d->pad; a.N = d->n;
     // cfg 0 runs as the 8-wave 256 x 128 instance (same tile, grid and rows)
     const int cfg = p.cfg == 1 ? 1 : 2;
     const int bm = kCfg[cfg].bm, bn = kCfg[cfg].bn;

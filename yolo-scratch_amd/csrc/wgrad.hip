@@ -622,7 +622,8 @@ struct WgPlan {
 // Round 5: 160 measured +0.2 % img/s in the step (three same-box pairs, profiles/r05/wgrad_target_streams_ab.txt) but
 // each launch ran longer alone (the 3x3 family's single-stream roofline fraction 0.2107 -> 0.1974, wgrad 0.199 ->
 // 0.161, profiles/r05/at_589d336): kept at 256, the gain inside the run-to-run spread
-Policy g_wg_target{256};
+// Each entry point reads it once and hands wg_plan the value.
+static Policy g_wg_target{256};
 
 // tap lookahead of the shipped wgrad3 instances (wgrad3_kernel LA)
 constexpr int kWgLA = 0;
@@ -630,7 +631,7 @@ constexpr int kWgLA = 0;
 Policy g_wg_la{kWgLA};
 #endif
 
-WgPlan wg_plan(const ym_conv_desc* d) {
+WgPlan wg_plan(const ym_conv_desc* d, int wg_target) {
     WgPlan p{};
     const int64_t M = int64_t(d->n) * d->oh * d->ow;
     const bool whole = d->x_bs == int64_t(d->h) * d->w * d->x_ld && d->y_bs == int64_t(d->oh) * d->ow * d->y_ld;
@@ -665,12 +666,12 @@ WgPlan wg_plan(const ym_conv_desc* d) {
     // 3x3: 147 KB, about the input an 8x8-pixel unit moves 12 times)
     int64_t min_units = p.kind == 3 ? 12 : 8;
     // workgroups per launch (g_wg_target above; round 1: 256 vs 512 / 1024 in the step)
-    int64_t target = g_wg_target;
+    int64_t target = wg_target;
     // stride-1 3x3 layers with few units per channel tile (20x20 maps, 256-channel 40x40): twice the target (512 when it
     // was 256) in workgroups of >= 6 units — the larger partials cost less than half the CUs idling (s@640 bs64, same-process A/B:
     // 128->128 20x20 34.7 -> 30.2 us, 256->128 40x40 84.8 -> 76.1 us; the stride-2 20x20 layers and
     // 128-channel 40x40 ones measured slower, so they keep 256)
-    if (p.kind == 3 && d->stride == 1 && p.units / cols < 256) { target = 2 * g_wg_target; min_units = 6; }
+    if (p.kind == 3 && d->stride == 1 && p.units / cols < 256) { target = 2 * wg_target; min_units = 6; }
     // the second register set pays where a split runs many units (maps >= 64 wide: 80x80 128->128
     // 152.8 -> 147.6 us); below that the extra VGPRs (120 -> 166: one workgroup per CU) cost as much
     p.deep = p.kind == 3 && d->ow >= 64;
@@ -733,7 +734,7 @@ void wg3_launch(const ym_conv_desc* d, const WgPlan& p, const WgArgs& a, dim3 gr
 }
 
 int wgrad_kernel(const ym_conv_desc* d, char* name, size_t len) {
-    const WgPlan p = wg_plan(d);
+    const WgPlan p = wg_plan(d, g_wg_target);
     if (p.kind == 3) {
         const int tc = (p.T == 32 ? 1 : 0) | (p.T2 == 32 ? 2 : 0);
         const bool db = d->stride == 1 || p.deep;        // two LDS buffers (ym_conv_wgrad)
@@ -756,7 +757,7 @@ using namespace ym;
 
 extern "C" size_t ym_conv_wgrad_workspace_size(const ym_conv_desc* d) {
     if (!d) return 0;
-    const WgPlan p = wg_plan(d);
+    const WgPlan p = wg_plan(d, g_wg_target);
     const int64_t E = int64_t(d->cout) * d->k * d->k * d->cin;
     return size_t((p.kind == 0 ? 1 : p.splits) * E) * sizeof(float);
 }
@@ -767,7 +768,7 @@ extern "C" int ym_conv_wgrad(const ym_conv_desc* d, const uint16_t* dz, const ui
     YM_CHECK_ARG(d->cin % 8 == 0 && d->cout % 8 == 0, "ym_conv_wgrad: channels %% 8 != 0");
     YM_CHECK_ARG(d->x_ld % 8 == 0 && d->y_ld % 8 == 0 && d->x_bs % 8 == 0 && d->y_bs % 8 == 0,
                  "ym_conv_wgrad: views not 16-byte aligned");
-    const WgPlan p = wg_plan(d);
+    const WgPlan p = wg_plan(d, g_wg_target);
     const int taps = d->k * d->k;
     const int64_t E = int64_t(d->cout) * taps * d->cin;
     const size_t need = size_t((p.kind == 0 ? 1 : p.splits) * E) * sizeof(float);
