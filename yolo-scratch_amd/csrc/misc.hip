@@ -357,10 +357,286 @@ __global__ void __launch_bounds__(256) sppf_bwd_kernel(const uint8_t* __restrict
     }
 }
 
+// Vector forms of the fused chain: a work item is (pixel, V consecutive channels), V = 8 or 4, and a
+// block owns one image x V channels, so the [HW][V] planes are the scalar kernels' [HW][CG] ones and
+// an item's values are one or two 16-byte LDS accesses.  A thread's items are the same on all three
+// levels (pixels tid, tid + 256, ...): the first one's (h, w) is divided out once, before the level
+// loop, and each next one follows by adding (256 / W, 256 % W) with one carry (a per-thread array of
+// decomposed items needs the item loop unrolled, and that took the backward to 207-256 VGPRs with spills
+// at 8 items per thread); the window clipping is shared by the V channels, and all global traffic is V
+// elements wide.  Same scans, update rule and summation order per channel as the scalar kernels:
+// bit-identical results.  Needs every pointer and stride aligned to V elements (view_aligned); other
+// calls take the scalar kernels.
+struct pix_walk {   // (h, w) of the pixels tid + 256 t of a W-wide map
+    int h, w, dh, dw, W;
+    __device__ pix_walk(int tid, int W_) : W(W_) {
+        h = tid / W; w = tid - h * W;
+        dh = 256 / W; dw = 256 - dh * W;
+    }
+    __device__ void next(int& ih, int& iw) const {
+        ih += dh; iw += dw;
+        if (iw >= W) { iw -= W; ++ih; }
+    }
+};
+// The blocks of one image (its C / V channel groups) write neighbouring 8..32-byte pieces of the same
+// cache lines — codes, fp16 / bf16 slices, fp32 rows.  Workgroups go to the 8 XCDs round-robin by linear id
+// (block b runs on XCD b % 8), so in plain order those pieces arrive in 8 different L2s and leave as partial
+// lines.  This maps the linear id so that each XCD runs a contiguous range of (image, channel group) blocks
+// in order: a line's pieces meet in one L2 at about the same time.  (The tail beyond a multiple of 8 maps
+// to itself.)
+__device__ __forceinline__ int xcd_chunked(int b, int total) {
+    const int per = total >> 3;
+    return b < per * 8 ? (b & 7) * per + (b >> 3) : b;
+}
+template <int V>
+__device__ __forceinline__ void vec_get(const float* p, float* f) {
+#pragma unroll
+    for (int i = 0; i < V / 4; ++i) {
+        const float4 v = reinterpret_cast<const float4*>(p)[i];
+        f[4 * i] = v.x; f[4 * i + 1] = v.y; f[4 * i + 2] = v.z; f[4 * i + 3] = v.w;
+    }
+}
+template <int V>
+__device__ __forceinline__ void vec_put(float* p, const float* f) {
+#pragma unroll
+    for (int i = 0; i < V / 4; ++i)
+        reinterpret_cast<float4*>(p)[i] = make_float4(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]);
+}
+// V bytes <-> V / 4 words (byte r of the run in bits 8 * (r % 4) of word r / 4)
+template <int V>
+__device__ __forceinline__ void bytes_get(const uint8_t* p, uint32_t* k) {
+    if constexpr (V == 8) {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        k[0] = v.x; k[1] = v.y;
+    } else {
+        k[0] = *reinterpret_cast<const uint32_t*>(p);
+    }
+}
+template <int V>
+__device__ __forceinline__ void bytes_put(uint8_t* p, const uint32_t* k) {
+    if constexpr (V == 8)
+        *reinterpret_cast<uint2*>(p) = make_uint2(k[0], k[1]);
+    else
+        *reinterpret_cast<uint32_t*>(p) = k[0];
+}
+// V bf16 gradients -> fp32
+template <int V>
+__device__ __forceinline__ void bf_get(const uint16_t* p, float* f) {
+    uint32_t w[V / 2];
+    if constexpr (V == 8) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        w[0] = v.x; w[1] = v.y;
+    }
+#pragma unroll
+    for (int i = 0; i < V / 2; ++i) {
+        f[2 * i] = bf2f(bf16_t(w[i] & 0xffff));
+        f[2 * i + 1] = bf2f(bf16_t(w[i] >> 16));
+    }
+}
+// V packed 16-bit pairs out
+template <int V>
+__device__ __forceinline__ void pairs_put(uint16_t* p, const uint32_t* w) {
+    if constexpr (V == 8)
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    else
+        *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) sppf_fwd_vec_kernel(const float* __restrict__ x, uint8_t* __restrict__ code,
+                                                           int64_t plane, uint16_t* __restrict__ y1,
+                                                           uint16_t* __restrict__ y2, uint16_t* __restrict__ y3,
+                                                           int64_t y_bs, int64_t y_ld, float* __restrict__ p_out, int H,
+                                                           int W, int C) {
+    extern __shared__ __attribute__((aligned(16))) float smv[];
+    const int HW = H * W, E = HW * V;
+    float* xs = smv;                                           // the current pool's input [HW][V], then its output
+    float* rm = smv + E;                                       // row maxima
+    uint8_t* rk = reinterpret_cast<uint8_t*>(smv + 2 * E);     // their kw
+    const int blk = xcd_chunked(blockIdx.x, gridDim.x), G = C / V, n = blk / G, c0 = (blk - n * G) * V;
+    const size_t base = (size_t(n) * HW) * C + c0;
+    const pix_walk walk(threadIdx.x, W);
+    for (int pix = threadIdx.x; pix < HW; pix += 256) {
+        float v[V];
+        vec_get<V>(x + base + size_t(pix) * C, v);
+        vec_put<V>(xs + pix * V, v);
+    }
+    __syncthreads();
+    // A tap outside the map is clamped onto the map's edge, with the kw / kh of the element it then reads: it
+    // repeats a tap of the same scan (the first valid one on the low side, the last on the high side), and the
+    // update rule applied twice to one (value, position) changes nothing, NaN included.  So the scan has no
+    // branches, starts from its tap 0 (the reference's `first`), and all five reads are in flight together.
+#pragma unroll 1
+    for (int j = 0; j < 3; ++j) {
+        uint16_t* yv = j == 0 ? y1 : j == 1 ? y2 : y3;
+        int h = walk.h, w = walk.w;
+#pragma unroll 1
+        for (int pix = threadIdx.x; pix < HW; pix += 256, walk.next(h, w)) {
+            float v[5][V], mx[V];
+            uint32_t kk[5], k[V];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) {
+                const int iw = min(max(w + d - 2, 0), W - 1);
+                kk[d] = uint32_t(iw - w + 2);
+                vec_get<V>(xs + (h * W + iw) * V, v[d]);
+            }
+#pragma unroll
+            for (int r = 0; r < V; ++r) { mx[r] = v[0][r]; k[r] = kk[0]; }
+#pragma unroll
+            for (int d = 1; d < 5; ++d)
+#pragma unroll
+                for (int r = 0; r < V; ++r)
+                    if (v[d][r] > mx[r] || v[d][r] != v[d][r]) { mx[r] = v[d][r]; k[r] = kk[d]; }
+            vec_put<V>(rm + pix * V, mx);
+            uint32_t kp[V / 4];
+#pragma unroll
+            for (int i = 0; i < V / 4; ++i)
+                kp[i] = k[4 * i] | (k[4 * i + 1] << 8) | (k[4 * i + 2] << 16) | (k[4 * i + 3] << 24);
+            bytes_put<V>(rk + pix * V, kp);
+        }
+        __syncthreads();
+        h = walk.h, w = walk.w;
+#pragma unroll 1
+        for (int pix = threadIdx.x; pix < HW; pix += 256, walk.next(h, w)) {
+            float v[5][V], mx[V];
+            uint32_t kq[5][V / 4], cd[V];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) {
+                const int ih = min(max(h + d - 2, 0), H - 1);
+                const int q = (ih * W + w) * V;
+                vec_get<V>(rm + q, v[d]);
+                bytes_get<V>(rk + q, kq[d]);
+                // the candidate codes (kh * 5 + kw) of the row, a byte each: no carries, they stay under 25
+#pragma unroll
+                for (int i = 0; i < V / 4; ++i) kq[d][i] += uint32_t((ih - h + 2) * 5) * 0x01010101u;
+            }
+#pragma unroll
+            for (int r = 0; r < V; ++r) { mx[r] = v[0][r]; cd[r] = (kq[0][r / 4] >> (8 * (r % 4))) & 0xff; }
+#pragma unroll
+            for (int d = 1; d < 5; ++d)
+#pragma unroll
+                for (int r = 0; r < V; ++r)
+                    if (v[d][r] > mx[r] || v[d][r] != v[d][r]) {
+                        mx[r] = v[d][r];
+                        cd[r] = (kq[d][r / 4] >> (8 * (r % 4))) & 0xff;
+                    }
+            const size_t o = base + size_t(pix) * C;
+            vec_put<V>(xs + pix * V, mx);                      // the row pass is done with xs: the next pool's input
+            uint32_t cp[V / 4], hp[V / 2];
+#pragma unroll
+            for (int i = 0; i < V / 4; ++i)
+                cp[i] = cd[4 * i] | (cd[4 * i + 1] << 8) | (cd[4 * i + 2] << 16) | (cd[4 * i + 3] << 24);
+#pragma unroll
+            for (int i = 0; i < V / 2; ++i) hp[i] = pk2h(mx[2 * i], mx[2 * i + 1]);
+            bytes_put<V>(code + j * plane + o, cp);
+            if (p_out) vec_put<V>(p_out + j * plane + o, mx);
+            pairs_put<V>(yv + n * y_bs + int64_t(pix) * y_ld + c0, hp);
+        }
+        __syncthreads();
+    }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) sppf_bwd_vec_kernel(const uint8_t* __restrict__ code, int64_t plane,
+                                                           const uint16_t* __restrict__ g1,
+                                                           const uint16_t* __restrict__ g2,
+                                                           const uint16_t* __restrict__ g3, int64_t g_bs, int64_t g_ld,
+                                                           uint16_t* __restrict__ dxv, int64_t v_bs, int64_t v_ld,
+                                                           int accumulate, float* __restrict__ dx32, int H, int W,
+                                                           int C) {
+    extern __shared__ __attribute__((aligned(16))) float smv[];
+    const int HW = H * W, E = HW * V;
+    float* gs = smv;                                           // routed gradient of the current pool output
+    float* ns = smv + E;                                       // the next one
+    uint8_t* kall = reinterpret_cast<uint8_t*>(smv + 2 * E);   // the three pools' codes [3][HW][V]
+    const int blk = xcd_chunked(blockIdx.x, gridDim.x), G = C / V, n = blk / G, c0 = (blk - n * G) * V;
+    const size_t base = (size_t(n) * HW) * C + c0;
+    const pix_walk walk(threadIdx.x, W);
+    // everything the chain reads from memory up front, in one round trip (the slice gradients g2 / g1 join
+    // at their level, loaded ahead of that level's gather)
+    for (int pix = threadIdx.x; pix < HW; pix += 256) {
+        float g[V];
+        uint32_t k[3][V / 4];
+        bf_get<V>(g3 + n * g_bs + int64_t(pix) * g_ld + c0, g);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) bytes_get<V>(code + j * plane + base + size_t(pix) * C, k[j]);
+        vec_put<V>(gs + pix * V, g);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) bytes_put<V>(kall + j * E + pix * V, k[j]);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int j = 2; j >= 0; --j) {
+        const uint16_t* init = j == 2 ? g2 : j == 1 ? g1 : nullptr;
+        const uint8_t* ks = kall + j * E;
+        int h = walk.h, w = walk.w;
+#pragma unroll 1
+        for (int pix = threadIdx.x; pix < HW; pix += 256, walk.next(h, w)) {
+            // the window clipped once per item: a position outside the map reads the item's own pixel
+            // against a code no pool writes (255), so it adds +0 like every other non-match
+            int qc[5];
+            bool okc[5];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) {
+                okc[d] = unsigned(w + d - 2) < unsigned(W);
+                qc[d] = okc[d] ? w + d - 2 : w;
+            }
+            float acc[V], b[V];
+#pragma unroll
+            for (int r = 0; r < V; ++r) acc[r] = 0.f;
+            uint16_t* p = dxv + n * v_bs + int64_t(pix) * v_ld + c0;
+            if (init) bf_get<V>(init + n * g_bs + int64_t(pix) * g_ld + c0, b);
+            else if (accumulate) bf_get<V>(p, b);
+#pragma unroll 1
+            for (int dh = -2; dh <= 2; ++dh) {
+                const bool okr = unsigned(h + dh) < unsigned(H);
+                const int row = (okr ? h + dh : h) * W;
+#pragma unroll
+                for (int d = 0; d < 5; ++d) {
+                    // the window at (h + dh, w + d - 2) sees this pixel at offset (-dh, 2 - d)
+                    const uint32_t want = okr && okc[d] ? uint32_t((2 - dh) * 5 + (4 - d)) : 255u;
+                    const int q = (row + qc[d]) * V;
+                    uint32_t k[V / 4];
+                    float g[V];
+                    bytes_get<V>(ks + q, k);
+                    vec_get<V>(gs + q, g);
+                    // +0 for a non-match is exact: the sum starts at +0 and so never holds -0
+#pragma unroll
+                    for (int r = 0; r < V; ++r)
+                        acc[r] += ((k[r / 4] >> (8 * (r % 4))) & 0xff) == want ? g[r] : 0.f;
+                }
+            }
+            if (j > 0) {
+#pragma unroll
+                for (int r = 0; r < V; ++r) acc[r] += b[r];
+                vec_put<V>(ns + pix * V, acc);
+            } else {
+                if (dx32) vec_put<V>(dx32 + base + size_t(pix) * C, acc);
+                if (accumulate) {
+#pragma unroll
+                    for (int r = 0; r < V; ++r) acc[r] += b[r];
+                }
+                uint32_t o[V / 2];
+#pragma unroll
+                for (int i = 0; i < V / 2; ++i) o[i] = pk2bf(acc[2 * i], acc[2 * i + 1]);
+                pairs_put<V>(p, o);
+            }
+        }
+        __syncthreads();
+        float* t = gs; gs = ns; ns = t;
+    }
+}
+
 // channels per block of the fused chain (0: the map does not fit, use the per-pool launches): the
-// forward on 8-channel blocks where they fit, the backward on 4-channel blocks (measured at s@640
-// 64x20x20x256: 232 / 154 us on 8 / 4 channels — its three dependent gather levels per block want
-// more blocks per CU; 2-channel blocks 175 us)
+// scalar forward on 8-channel blocks where they fit, the scalar backward on 4-channel blocks (at s@640
+// 64x20x20x256 it ran 232 / 154 us on 8 / 4 channels, 2-channel blocks 175 us).  Calls whose views are
+// aligned take the vector kernels above, whose items are this many channels wide: at the same shape
+// 120 -> 45 us forward, 146 -> 68 us backward alone, 125 -> 45 / 198 -> 106 us in the step
+// (profiles/pool/).  Of that, 80 -> 45 and 95 -> 68 us came from running one image's channel groups on
+// one XCD (xcd_chunked); the vector items alone gave 120 -> 80 and 146 -> 96 us.
 int sppf_cg(int h, int w, int c) {
     const int64_t hw = int64_t(h) * w;
     if (c % 8 == 0 && hw * 8 * 13 <= 96 * 1024) return 8;
@@ -374,6 +650,12 @@ static int sppf_cg_fwd(int n, int h, int w, int c) {
     int cg = sppf_cg(h, w, c);
     while (cg > 1 && int64_t(n) * (c / cg) < 256) cg >>= 1;
     return cg;
+}
+// the vector kernels' granule: V elements of every view — V x 2 bytes of a 16-bit view, V bytes of
+// codes, 16 bytes of fp32 (V >= 4 floats a pixel)
+static bool ptr_aligned(const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+static bool view_aligned(const void* p, int64_t bs, int64_t ld, int v) {
+    return ptr_aligned(p, size_t(v) * 2) && bs % v == 0 && ld % v == 0;
 }
 
 // channels per block of the LDS forms (0: the map does not fit, use the direct kernels)
@@ -399,32 +681,42 @@ __global__ void upsample2_fwd_kernel(const bf16_t* __restrict__ x, int64_t x_bs,
     }
 }
 
-__global__ void upsample2_bwd_kernel(const bf16_t* __restrict__ dy, int64_t d_bs, int64_t d_ld, bf16_t* __restrict__ dx,
-                                     int64_t x_bs, int64_t x_ld, int N, int H, int W, int C, int accumulate) {
-    const int cg = C / 8, OW = 2 * W;
-    const int64_t total = int64_t(N) * H * W * cg;
-    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += int64_t(gridDim.x) * blockDim.x) {
-        int g = int(i % cg);
-        int64_t m = i / cg;
-        int64_t n = m / (int64_t(H) * W), pix = m - n * H * W;
-        int h = int(pix / W), w = int(pix % W);
-        float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < 2; ++b) {
+// The grid hands a thread its image (z), input row (y) and position in the row's W x C/8 channel groups (x): one
+// 32-bit division per 16 bytes of dx where a flat 64-bit index cost four 64-bit ones.  The four loads are issued
+// before the first sum; the sum keeps the order (0,0), (0,1), (1,0), (1,1), then the existing gradient.  Alone the
+// kernel streams at its memory rate either way (20 / 38 us at the two s@640 bs64 shapes before and after); in the
+// step the two calls went 150 -> 132 us, the rest above memory time being contention with the side streams.
+__global__ void __launch_bounds__(256) upsample2_bwd_kernel(const bf16_t* __restrict__ dy, int64_t d_bs, int64_t d_ld,
+                                                            bf16_t* __restrict__ dx, int64_t x_bs, int64_t x_ld, int N,
+                                                            int H, int W, int C, int accumulate) {
+    const unsigned cg = unsigned(C) / 8, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= unsigned(W) * cg) return;
+    const unsigned w = i / cg, g = i - w * cg;
+    for (int n = blockIdx.z; n < N; n += gridDim.z)
+        for (int h = blockIdx.y; h < H; h += gridDim.y) {
+            const bf16_t* r0 = dy + n * d_bs + (int64_t(2 * h) * (2 * W) + 2 * w) * d_ld + g * 8;
+            const bf16_t* r1 = r0 + int64_t(2 * W) * d_ld;
+            bf16_t* o = dx + n * x_bs + (int64_t(h) * W + w) * x_ld + g * 8;
+            const uint4 q[4] = {*reinterpret_cast<const uint4*>(r0), *reinterpret_cast<const uint4*>(r0 + d_ld),
+                                *reinterpret_cast<const uint4*>(r1), *reinterpret_cast<const uint4*>(r1 + d_ld)};
+            uint4 old = make_uint4(0, 0, 0, 0);
+            if (accumulate) old = *reinterpret_cast<const uint4*>(o);
+            float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
                 float v[8];
-                unpack8(*reinterpret_cast<const uint4*>(dy + n * d_bs + (int64_t(2 * h + a) * OW + 2 * w + b) * d_ld + g * 8), v);
+                unpack8(q[t], v);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) s[k] += v[k];
             }
-        bf16_t* o = dx + n * x_bs + pix * x_ld + g * 8;
-        if (accumulate) {
-            float v[8];
-            unpack8(*reinterpret_cast<const uint4*>(o), v);
+            if (accumulate) {
+                float v[8];
+                unpack8(old, v);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) s[k] += v[k];
+                for (int k = 0; k < 8; ++k) s[k] += v[k];
+            }
+            *reinterpret_cast<uint4*>(o) = pack8(s);
         }
-        *reinterpret_cast<uint4*>(o) = pack8(s);
-    }
 }
 
 // ------------------------------------------------------------------ conversions
@@ -628,6 +920,22 @@ extern "C" int ym_sppf_fwd(const float* x, uint8_t* code, uint16_t* y1, uint16_t
     YM_CHECK_ARG(int64_t(n) * h * w * c < (int64_t(1) << 31), "ym_sppf_fwd: too large");
     if (n == 0) return YM_OK;
     const int64_t plane = int64_t(n) * h * w * c;
+    // vector items of 8 channels, of 4 where only those fit or the grid would hold under 256 blocks
+    int v = sppf_cg(h, w, c);
+    if (v == 8 && int64_t(n) * (c / 8) < 256) v = 4;
+    if (ptr_aligned(x, 16) && ptr_aligned(code, v) && (!p_out || ptr_aligned(p_out, 16)) &&
+        view_aligned(y1, y_bs, y_ld, v) && view_aligned(y2, y_bs, y_ld, v) && view_aligned(y3, y_bs, y_ld, v)) {
+        const size_t vlds = size_t(h) * w * v * 9;
+        const dim3 vgrid(unsigned(int64_t(n) * (c / v)));
+        if (v == 8)
+            hipLaunchKernelGGL(sppf_fwd_vec_kernel<8>, vgrid, dim3(256), vlds, as_stream(stream), x, code, plane, y1, y2,
+                               y3, y_bs, y_ld, p_out, h, w, c);
+        else
+            hipLaunchKernelGGL(sppf_fwd_vec_kernel<4>, vgrid, dim3(256), vlds, as_stream(stream), x, code, plane, y1, y2,
+                               y3, y_bs, y_ld, p_out, h, w, c);
+        YM_LAUNCH_CHECK("ym_sppf_fwd");
+        return YM_OK;
+    }
     const size_t lds = size_t(h) * w * cg * 13;
     const dim3 grid(unsigned(c / cg), unsigned(n));
     if (cg == 8)
@@ -655,6 +963,20 @@ extern "C" int ym_sppf_bwd(const uint8_t* code, const uint16_t* g1, const uint16
     YM_CHECK_ARG(int64_t(n) * h * w * c < (int64_t(1) << 31), "ym_sppf_bwd: too large");
     if (n == 0) return YM_OK;
     const int64_t plane = int64_t(n) * h * w * c;
+    const int v = sppf_cg(h, w, c);
+    if (ptr_aligned(code, v) && (!dx32 || ptr_aligned(dx32, 16)) && view_aligned(g1, g_bs, g_ld, v) &&
+        view_aligned(g2, g_bs, g_ld, v) && view_aligned(g3, g_bs, g_ld, v) && view_aligned(dxv, v_bs, v_ld, v)) {
+        const size_t vlds = size_t(h) * w * v * 11;
+        const dim3 vgrid(unsigned(int64_t(n) * (c / v)));
+        if (v == 8)
+            hipLaunchKernelGGL(sppf_bwd_vec_kernel<8>, vgrid, dim3(256), vlds, as_stream(stream), code, plane, g1, g2, g3,
+                               g_bs, g_ld, dxv, v_bs, v_ld, accumulate, dx32, h, w, c);
+        else
+            hipLaunchKernelGGL(sppf_bwd_vec_kernel<4>, vgrid, dim3(256), vlds, as_stream(stream), code, plane, g1, g2, g3,
+                               g_bs, g_ld, dxv, v_bs, v_ld, accumulate, dx32, h, w, c);
+        YM_LAUNCH_CHECK("ym_sppf_bwd");
+        return YM_OK;
+    }
     const size_t lds = size_t(h) * w * cg * 9;
     hipLaunchKernelGGL(sppf_bwd_kernel<4>, dim3(unsigned(c / 4), unsigned(n)), dim3(256), lds, as_stream(stream), code,
                        plane, g1, g2, g3, g_bs, g_ld, dxv, v_bs, v_ld, accumulate, dx32, h, w, c);
@@ -674,8 +996,15 @@ extern "C" int ym_upsample2_fwd(const uint16_t* x, int64_t x_bs, int64_t x_ld, u
 extern "C" int ym_upsample2_bwd(const uint16_t* dy, int64_t d_bs, int64_t d_ld, uint16_t* dx, int64_t x_bs,
                                 int64_t x_ld, int n, int h, int w, int c, int accumulate, void* stream) {
     YM_CHECK_ARG(c % 8 == 0 && VIEW_ALIGNED(d_bs, d_ld) && VIEW_ALIGNED(x_bs, x_ld), "ym_upsample2_bwd: alignment");
-    hipLaunchKernelGGL(upsample2_bwd_kernel, dim3(grid_for(int64_t(n) * h * w * (c / 8))), dim3(256), 0,
-                       as_stream(stream), dy, d_bs, d_ld, dx, x_bs, x_ld, n, h, w, c, accumulate);
+    // the kernel's 32-bit row index (w x c / 8) and its 2 h, 2 w
+    YM_CHECK_ARG(n >= 0 && h >= 0 && w >= 0 && c >= 0 && int64_t(w) * (c / 8) < (int64_t(1) << 31) &&
+                     h < (1 << 30) && w < (1 << 30),
+                 "ym_upsample2_bwd: too large");
+    if (n == 0 || h == 0 || w == 0 || c == 0) return YM_OK;
+    const dim3 grid(unsigned((int64_t(w) * (c / 8) + 255) / 256), unsigned(std::min(h, 65535)),
+                    unsigned(std::min(n, 65535)));
+    hipLaunchKernelGGL(upsample2_bwd_kernel, grid, dim3(256), 0, as_stream(stream), dy, d_bs, d_ld, dx, x_bs, x_ld, n, h,
+                       w, c, accumulate);
     YM_LAUNCH_CHECK("ym_upsample2_bwd");
     return YM_OK;
 }
