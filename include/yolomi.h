@@ -504,6 +504,25 @@ typedef struct ym_aug_entry {
 int ym_augment_u8(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev, int batch, int size,
                   float* out, void* stream);
 
+/* The same two for images of `ch` = 1..4 planes.  `src` holds pixel-interleaved images (h0, w0, ch) back to back,
+ * as an image decoder yields them; meta[3b..] stays {byte offset, h0, w0} and image b occupies h0 * w0 * ch bytes;
+ * `out` is planar (batch, ch, size, size) fp32, the stem's input.  The geometry (slot, tile, taps, weights, fill)
+ * is formed once per output pixel and every plane is blended at the same taps, then goes through the gain; with
+ * ch == 1 the two are ym_resize_linear_u8 / ym_augment_u8 bit for bit.
+ * `colour_dev` (NULL: none; needs ch == 3) holds one ym_aug_colour per image: a hue shift and a saturation factor
+ * applied to (r, g, b) after sampling and before the gain, in integers on the HSV hexcone with V kept
+ * (include/yolomi_augment.h: ym_aug_hue_sat):
+ *   hue  Q16 fraction of a turn, taken & 65535 (a shift, as torchvision's adjust_hue)
+ *   sat  Q16 factor on the chroma V - min, clamped to [0, 2^17] */
+typedef struct ym_aug_colour {
+    int32_t hue;
+    int32_t sat;
+} ym_aug_colour;
+int ym_resize_linear_u8c(const uint8_t* src, const int64_t* meta, int batch, int ch, int size, float* out,
+                         void* stream);
+int ym_augment_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
+                   const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out, void* stream);
+
 /* ------------------------------------------------------------------ optimizer tail
  * clip_grad_norm_(params, max_norm) + AdamW.step() over every parameter (train_yolo11_cuda.py:58-62,
  * 440-451).  The parameters form one flat index space: entry e covers elements [offset, offset + n)

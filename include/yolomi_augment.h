@@ -125,4 +125,131 @@ YM_HD static inline int ym_aug_sample(const uint8_t* src, const int64_t* meta, i
     return ym_aug_gain(e->gain, ym_aug_tile_value(src, meta, batch, e->fill, &e->tile[slot], cx, cy, x, y));
 }
 
+/* ---------------------------------------------------------------- 1-4 planes (ym_resize_linear_u8c, ym_augment_u8c)
+ * The source is pixel-interleaved (h0, w0, ch).  Everything above that does not touch a source byte (slot, tile
+ * and rectangle test, tap indices, weights, fill) is formed once per output pixel into ym_aug_taps; every plane is
+ * then ym_aug_blend's arithmetic on bytes `ch` apart, and goes through ym_aug_gain.  With ch == 1 the values are
+ * ym_aug_sample's.
+ *
+ * Hue and saturation (ch == 3, between sampling and the gain) work on the HSV hexcone in integers and keep V:
+ *   V = max, m = min, d = V - m; d == 0 leaves the pixel alone
+ *   H6 in [0, 6d) the position on the hexcone (sector * d + offset, red first, then green)
+ *   H6' = (H6 + ((hue * 6d + 32768) >> 16)) % 6d     hue Q16 fraction of a turn, & 65535: a shift
+ *   d'  = min((d * sat) >> 16, V)                    sat Q16, clamped to [0, 2^17]
+ *   k = H6' / d, f = H6' - k d, f' = (2 f d' + d) / (2d), m' = V - d'; the sector k places V, m' and m' + f' or V - f'
+ * hue = 0, sat = 65536 returns the input bytes.  Against the real-valued hexcone the error is at most 2.5 levels for
+ * sat <= 2: 0.5 from the rounded shift scaled by d'/d <= 2, 1 from the truncation of d', 0.5 from f'. */
+typedef struct ym_aug_taps {
+    const uint8_t* r0;         /* plane 0 of the first pixel of rows sy and min(sy + 1, h0 - 1) */
+    const uint8_t* r1;
+    int64_t o0, o1;            /* byte offsets of columns sx and min(sx + 1, w0 - 1) in a row */
+    int a0, a1, b0, b1;
+} ym_aug_taps;
+
+YM_HD static inline void ym_aug_set_taps(const uint8_t* im, int h0, int w0, int ch, int sx, int a0, int a1, int sy,
+                                         int b0, int b1, ym_aug_taps& t) {
+    const int sx1 = sx + 1 < w0 ? sx + 1 : w0 - 1, sy1 = sy + 1 < h0 ? sy + 1 : h0 - 1;
+    const int64_t row = int64_t(w0) * ch;
+    t.r0 = im + int64_t(sy) * row;
+    t.r1 = im + int64_t(sy1) * row;
+    t.o0 = int64_t(sx) * ch;
+    t.o1 = int64_t(sx1) * ch;
+    t.a0 = a0, t.a1 = a1, t.b0 = b0, t.b1 = b1;
+}
+
+/* ym_aug_blend at the taps `t`, plane c */
+YM_HD static inline int ym_aug_taps_value(const ym_aug_taps& t, int c) {
+    const int h0v = int(t.r0[t.o0 + c]) * t.a0 + int(t.r0[t.o1 + c]) * t.a1;
+    const int h1v = int(t.r1[t.o0 + c]) * t.a0 + int(t.r1[t.o1 + c]) * t.a1;
+    int v = (((t.b0 * (h0v >> 4)) >> 16) + ((t.b1 * (h1v >> 4)) >> 16) + 2) >> 2;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+/* taps of ym_resize_linear_u8's rule for output pixel (x, y) of the h0 x w0 image at `im` */
+YM_HD static inline void ym_aug_lin_taps(const uint8_t* im, int h0, int w0, int ch, int S, int x, int y,
+                                         ym_aug_taps& t) {
+    int sx, a0, a1, sy, b0, b1;
+    ym_aug_lin_coeff(x, double(w0) / S, w0, sx, a0, a1);
+    ym_aug_lin_coeff(y, double(h0) / S, h0, sy, b0, b1);
+    ym_aug_set_taps(im, h0, w0, ch, sx, a0, a1, sy, b0, b1, t);
+}
+
+/* ym_aug_stretch_value's geometry; false: the pixel shows the fill */
+YM_HD static inline bool ym_aug_stretch_taps(const uint8_t* src, const int64_t* meta, int batch, int ch, int S,
+                                             const ym_aug_entry* e, int x, int y, ym_aug_taps& t) {
+    const int b = e->tile[0].src;
+    if (b < 0 || b >= batch) return false;
+    const int h0 = int(meta[3 * b + 1]), w0 = int(meta[3 * b + 2]);
+    if (h0 <= 0 || w0 <= 0) return false;
+    ym_aug_lin_taps(src + meta[3 * b], h0, w0, ch, S, x, y, t);
+    return true;
+}
+
+/* ym_aug_tile_value's geometry; false: the pixel shows the fill */
+YM_HD static inline bool ym_aug_tile_taps(const uint8_t* src, const int64_t* meta, int batch, int ch,
+                                          const ym_aug_tile* tl, int64_t cx, int64_t cy, int x, int y,
+                                          ym_aug_taps& t) {
+    const int b = tl->src;
+    if (b < 0 || b >= batch || cx < tl->x0 || cx >= tl->x1 || cy < tl->y0 || cy >= tl->y1) return false;
+    const int h0 = int(meta[3 * b + 1]), w0 = int(meta[3 * b + 2]);
+    if (h0 <= 0 || w0 <= 0) return false;
+    int sx, a0, a1, sy, b0, b1;
+    ym_aug_fix_coeff(ym_aug_map(tl->m, x, y), w0, sx, a0, a1);
+    ym_aug_fix_coeff(ym_aug_map(tl->m + 3, x, y), h0, sy, b0, b1);
+    ym_aug_set_taps(src + meta[3 * b], h0, w0, ch, sx, a0, a1, sy, b0, b1, t);
+    return true;
+}
+
+/* hue shift and saturation factor on 8-bit (r, g, b) = v[0..2], V kept (the rule is stated above) */
+YM_HD static inline void ym_aug_hue_sat(int hue, int sat, int* v) {
+    const int r = v[0], g = v[1], b = v[2];
+    const int V = r > g ? (r > b ? r : b) : (g > b ? g : b);
+    const int m = r < g ? (r < b ? r : b) : (g < b ? g : b);
+    const int d = V - m;
+    if (d == 0) return;
+    int H6;
+    if (V == r) H6 = g >= b ? g - b : 5 * d + (r - b);
+    else if (V == g) H6 = b >= r ? 2 * d + (b - r) : d + (g - r);
+    else H6 = r >= g ? 4 * d + (r - g) : 3 * d + (b - g);
+    H6 = (H6 + (((hue & 65535) * 6 * d + 32768) >> 16)) % (6 * d);
+    sat = sat < 0 ? 0 : (sat > (1 << 17) ? (1 << 17) : sat);
+    int d1 = (d * sat) >> 16;
+    d1 = d1 < V ? d1 : V;
+    const int k = H6 / d, f = H6 - k * d;
+    const int f1 = (2 * f * d1 + d) / (2 * d), m1 = V - d1;
+    const int up = m1 + f1, dn = V - f1;
+    switch (k) {
+        case 0: v[0] = V, v[1] = up, v[2] = m1; break;
+        case 1: v[0] = dn, v[1] = V, v[2] = m1; break;
+        case 2: v[0] = m1, v[1] = V, v[2] = up; break;
+        case 3: v[0] = m1, v[1] = dn, v[2] = V; break;
+        case 4: v[0] = up, v[1] = m1, v[2] = V; break;
+        default: v[0] = V, v[1] = m1, v[2] = dn; break;
+    }
+}
+
+/* the `ch` planes of a pixel whose geometry is known (`hit` false: fill): blend, hue / sat (`col` may be null;
+ * ch == 3 only), gain */
+YM_HD static inline void ym_aug_planes(const ym_aug_entry* e, const ym_aug_colour* col, int ch, bool hit,
+                                       const ym_aug_taps& t, int* v) {
+    for (int c = 0; c < ch; ++c) v[c] = hit ? ym_aug_taps_value(t, c) : (e->fill & 255);
+    if (col && ch == 3) ym_aug_hue_sat(col->hue, col->sat, v);
+    for (int c = 0; c < ch; ++c) v[c] = ym_aug_gain(e->gain, v[c]);
+}
+
+/* the `ch` values v[0..ch) of output pixel (x, y) of the image `e` describes; src / meta as for ym_augment_u8c */
+YM_HD static inline void ym_aug_sample_c(const uint8_t* src, const int64_t* meta, int batch, int ch, int S,
+                                         const ym_aug_entry* e, const ym_aug_colour* col, int x, int y, int* v) {
+    ym_aug_taps t = {};
+    bool hit;
+    if (e->flags & YM_AUG_STRETCH) {
+        hit = ym_aug_stretch_taps(src, meta, batch, ch, S, e, x, y, t);
+    } else {
+        int64_t cx, cy;
+        const int slot = ym_aug_slot(e, x, y, cx, cy);
+        hit = ym_aug_tile_taps(src, meta, batch, ch, &e->tile[slot], cx, cy, x, y, t);
+    }
+    ym_aug_planes(e, col, ch, hit, t, v);
+}
+
 #endif

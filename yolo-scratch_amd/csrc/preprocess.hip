@@ -107,6 +107,117 @@ __global__ void augment_u8_kernel(const uint8_t* __restrict__ src, const int64_t
     }
 }
 
+// ---- 1-4 planes (ym_resize_linear_u8c, ym_augment_u8c): pixel-interleaved source, planar output.  The launch shape
+// is augment_u8_kernel's; a pixel's geometry (slot, tile test, taps, weights) is formed once into ym_aug_taps and
+// the CH planes are blended at those taps (bytes CH apart), so a thread ends with CH 16-byte stores, one per plane.
+
+// `v[c][k]`: plane c of the thread's k-th pixel -> out planes at pixel p (SS pixels per plane)
+template <int CH>
+__device__ __forceinline__ void store_planes(float* __restrict__ o, int SS, int p, int vec, const float (&v)[CH][4]) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        float* oc = o + int64_t(c) * SS;
+        if (vec) {
+            *reinterpret_cast<float4*>(oc + p) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (p + k < SS) oc[p + k] = v[c][k];
+        }
+    }
+}
+
+// out (B, CH, S, S) fp32.  blockIdx.y walks images, so the image's size and the copy / stretch choice are
+// block-uniform.
+template <int CH>
+__global__ void resize_linear_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta, int batch,
+                                         int S, int vec, float* __restrict__ out) {
+    const int SS = S * S;
+    const int groups = (SS + 3) >> 2;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const uint8_t* im = src + meta[3 * b];
+        const int h0 = int(meta[3 * b + 1]), w0 = int(meta[3 * b + 2]);
+        const bool copy = h0 == S && w0 == S, empty = h0 <= 0 || w0 <= 0;
+        float* o = out + int64_t(b) * CH * SS;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / S, x = p - y * S;
+            float v[CH][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (p + k < SS && !empty) {
+                    if (copy) {
+                        const uint8_t* px = im + int64_t(p + k) * CH;
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(px[c]) / 255.0f;
+                    } else {
+                        ym_aug_taps t;
+                        ym_aug_lin_taps(im, h0, w0, CH, S, x, y, t);
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(ym_aug_taps_value(t, c)) / 255.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) v[c][k] = 0.f;
+                }
+                if (++x == S) { x = 0; ++y; }
+            }
+            store_planes<CH>(o, SS, p, vec, v);
+        }
+    }
+}
+
+// ym_aug_sample_c for a block-uniform entry `e` and colour entry `col` (may be null), with augment_pixel's
+// wave-uniform-slot path
+template <int CH>
+__device__ __forceinline__ void augment_pixel_c(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                                int batch, int S, const ym_aug_entry* __restrict__ e,
+                                                const ym_aug_colour* __restrict__ col, int x, int y, int* v) {
+    ym_aug_taps t = {};
+    bool hit;
+    if (e->flags & YM_AUG_STRETCH) {
+        hit = ym_aug_stretch_taps(src, meta, batch, CH, S, e, x, y, t);
+    } else {
+        int64_t cx, cy;
+        const int slot = ym_aug_slot(e, x, y, cx, cy);
+        const int first = __builtin_amdgcn_readfirstlane(slot);
+        if (__all(slot == first))
+            hit = ym_aug_tile_taps(src, meta, batch, CH, &e->tile[first], cx, cy, x, y, t);
+        else
+            hit = ym_aug_tile_taps(src, meta, batch, CH, &e->tile[slot], cx, cy, x, y, t);
+    }
+    ym_aug_planes(e, col, CH, hit, t, v);
+}
+
+// out (B, CH, S, S) fp32; `colour` null or one entry per image (CH == 3); `vec` as for augment_u8_kernel (a plane
+// is S * S floats, so every plane's groups are aligned when the first plane's are)
+template <int CH>
+__global__ void augment_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                   const ym_aug_entry* __restrict__ table, const ym_aug_colour* __restrict__ colour,
+                                   int batch, int S, int vec, float* __restrict__ out) {
+    const int SS = S * S;
+    const int groups = (SS + 3) >> 2;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const ym_aug_entry* e = table + b;
+        const ym_aug_colour* col = CH == 3 && colour ? colour + b : nullptr;
+        float* o = out + int64_t(b) * CH * SS;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / S, x = p - y * S;
+            float v[CH][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int u[CH] = {};
+                if (p + k < SS) augment_pixel_c<CH>(src, meta, batch, S, e, col, x, y, u);
+#pragma unroll
+                for (int c = 0; c < CH; ++c) v[c][k] = float(u[c]) / 255.0f;
+                if (++x == S) { x = 0; ++y; }
+            }
+            store_planes<CH>(o, SS, p, vec, v);
+        }
+    }
+}
+
 }  // namespace
 }  // namespace ym
 
@@ -136,5 +247,64 @@ extern "C" int ym_augment_u8(const uint8_t* src, const int64_t* meta, const ym_a
     hipLaunchKernelGGL(augment_u8_kernel, dim3(unsigned(bx), unsigned(std::min(batch, 65535))), dim3(256), 0,
                        as_stream(stream), src, meta, table_dev, batch, size, vec, out);
     YM_LAUNCH_CHECK("ym_augment_u8");
+    return YM_OK;
+}
+
+namespace {
+
+// grid of the per-image launch shape: blockIdx.x covers up to 256 blocks of groups (larger images grid-stride),
+// blockIdx.y the images
+dim3 image_grid(int batch, int size) {
+    const int64_t groups = (int64_t(size) * size + 3) / 4;
+    return dim3(unsigned(std::min<int64_t>((groups + 255) / 256, 256)), unsigned(std::min(batch, 65535)));
+}
+
+int planes_vec(int size, const float* out) {
+    return (int64_t(size) * size) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+}
+
+}  // namespace
+
+extern "C" int ym_resize_linear_u8c(const uint8_t* src, const int64_t* meta, int batch, int ch, int size, float* out,
+                                    void* stream) {
+    YM_CHECK_ARG(src && meta && out && batch >= 0 && size > 0 && size <= 32768 && ch >= 1 && ch <= 4,
+                 "ym_resize_linear_u8c: bad arguments (ch is 1..4)");
+    if (batch == 0) return YM_OK;
+    const dim3 grid = image_grid(batch, size);
+    const int vec = planes_vec(size, out);
+#define YM_RESIZE_C(CH)                                                                                          \
+    hipLaunchKernelGGL(resize_linear_u8c_kernel<CH>, grid, dim3(256), 0, as_stream(stream), src, meta, batch, size, \
+                       vec, out)
+    switch (ch) {
+        case 1: YM_RESIZE_C(1); break;
+        case 2: YM_RESIZE_C(2); break;
+        case 3: YM_RESIZE_C(3); break;
+        default: YM_RESIZE_C(4); break;
+    }
+#undef YM_RESIZE_C
+    YM_LAUNCH_CHECK("ym_resize_linear_u8c");
+    return YM_OK;
+}
+
+extern "C" int ym_augment_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
+                              const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out,
+                              void* stream) {
+    YM_CHECK_ARG(src && meta && table_dev && out && batch >= 0 && size > 0 && size <= 32768 && ch >= 1 && ch <= 4,
+                 "ym_augment_u8c: bad arguments (ch is 1..4)");
+    YM_CHECK_ARG(!colour_dev || ch == 3, "ym_augment_u8c: a colour table needs ch == 3 (got %d)", ch);
+    if (batch == 0) return YM_OK;
+    const dim3 grid = image_grid(batch, size);
+    const int vec = planes_vec(size, out);
+#define YM_AUGMENT_C(CH)                                                                                       \
+    hipLaunchKernelGGL(augment_u8c_kernel<CH>, grid, dim3(256), 0, as_stream(stream), src, meta, table_dev,    \
+                       colour_dev, batch, size, vec, out)
+    switch (ch) {
+        case 1: YM_AUGMENT_C(1); break;
+        case 2: YM_AUGMENT_C(2); break;
+        case 3: YM_AUGMENT_C(3); break;
+        default: YM_AUGMENT_C(4); break;
+    }
+#undef YM_AUGMENT_C
+    YM_LAUNCH_CHECK("ym_augment_u8c");
     return YM_OK;
 }

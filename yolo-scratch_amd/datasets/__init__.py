@@ -3,14 +3,16 @@
 CraterDatasetCUDA mirrors /root/reference/yolo_scratch_cuda/datasets/crater_dataset_cuda.py:26-286
 (decode in the workers, stretch-resize on the GPU: datasets/crater.py); collate_fn_cuda mirrors
 :289-346; prepare_batch is the device transfer of train_yolo11_cuda.py:43-45; BatchAugment (datasets/augment.py)
-is the training-time replacement of prepare_batch that augments on the GPU.
+is the training-time replacement of prepare_batch that augments on the GPU; YoloTxtDataset (datasets/yolo_txt.py)
+reads images/ + labels/*.txt datasets of 1, 3 or 4 planes through the same collate and the same two launches.
 """
 from .collate import collate_fn_cuda  # noqa: F401
 from .crater import CraterDatasetCUDA, max_gt_count, prepare_batch, resize_batch  # noqa: F401
 from .augment import AugmentHyp, BatchAugment  # noqa: F401
+from .yolo_txt import YoloTxtDataset  # noqa: F401
 
 collate_fn = collate_fn_cuda
 CraterDatasetYOLO = CraterDatasetCUDA
 
 __all__ = ["CraterDatasetCUDA", "CraterDatasetYOLO", "collate_fn_cuda", "collate_fn", "prepare_batch", "AugmentHyp",
-           "BatchAugment"]
+           "BatchAugment", "YoloTxtDataset"]

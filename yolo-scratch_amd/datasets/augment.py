@@ -15,6 +15,11 @@ Geometry (Ultralytics Mosaic + RandomPerspective without the perspective term), 
              uniform(0.5 - translate, 0.5 + translate) * S; the output is the S x S window at the origin
   flips      on the output (pixel index S - 1 - x; boxes 1 - x on the normalised coordinate)
 An image whose geometry is the identity is flagged YM_AUG_STRETCH and equals the validation path's resize bit for bit.
+
+Batches of 2-4 planes (pixel-interleaved images, `img_ch` in the batch dict: datasets/yolo_txt.py) go through
+ym_augment_u8c with the same table: the geometry is formed once per pixel, every plane is blended at the same taps and
+takes the gain.  On 3-plane batches `hsv_h` / `hsv_s` add a per-image hue shift and saturation factor (a second table
+of ym_aug_colour, appended to the first for the transfer); their uniforms are drawn after every other one.
 """
 from __future__ import annotations
 
@@ -25,7 +30,7 @@ import math
 import numpy as np
 import torch
 
-from yolomi._lib import AugEntry, AugTile
+from yolomi._lib import AugColour, AugEntry, AugTile
 
 FB = 24                        # YM_AUG_FB
 STRETCH = 1                    # YM_AUG_STRETCH
@@ -34,7 +39,9 @@ _I64_MAX = (1 << 63) - 1
 
 @dataclasses.dataclass
 class AugmentHyp:
-    """Hyperparameters, named as in Ultralytics' v8 trainer (`gain` is their hsv_v: the images are single-plane)."""
+    """Hyperparameters, named as in Ultralytics' v8 trainer (`gain` is their hsv_v and applies to every plane).
+    `hsv_h` (+/- fraction of a turn, a hue shift) and `hsv_s` (+/- fraction around 1, a saturation factor) act on
+    3-plane batches only and default to off: the 1-plane recipe is unchanged."""
     mosaic: float = 1.0
     degrees: float = 0.0
     translate: float = 0.1
@@ -44,10 +51,12 @@ class AugmentHyp:
     flipud: float = 0.0
     gain: float = 0.4
     fill: int = 114
+    hsv_h: float = 0.0
+    hsv_s: float = 0.0
 
     def is_off(self) -> bool:
         return not any((self.mosaic, self.degrees, self.translate, self.scale, self.shear, self.fliplr, self.flipud,
-                        self.gain))
+                        self.gain, self.hsv_h, self.hsv_s))
 
 
 def _fix(v) -> int:
@@ -176,21 +185,40 @@ def step_seed(seed: int, rank: int, epoch: int, step: int) -> int:
     return int(ss.generate_state(1, np.uint64)[0]) & _I64_MAX
 
 
-def augment_batch(img_u8: torch.Tensor, meta: torch.Tensor, table: torch.Tensor, img_size: int) -> torch.Tensor:
-    """GPU: packed uint8 images + device table of ym_aug_entry (uint8 bytes) -> (B, 1, S, S) fp32 (ym_augment_u8)."""
-    from yolomi._lib import call, require_device, stream_ptr
-    require_device(img_u8, meta, table)
+def augment_batch(img_u8: torch.Tensor, meta: torch.Tensor, table: torch.Tensor, img_size: int, channels: int = 1,
+                  colour: torch.Tensor | None = None) -> torch.Tensor:
+    """GPU: packed uint8 images + device table of ym_aug_entry (uint8 bytes) -> (B, channels, S, S) fp32
+    (ym_augment_u8; ym_augment_u8c for channels > 1, whose source is pixel-interleaved, or with `colour`, a device
+    table of ym_aug_colour as uint8 bytes, channels == 3 only)."""
+    from yolomi._lib import call, ptr, require_device, stream_ptr
+    require_device(img_u8, meta, table, colour)
     B = meta.shape[0]
     assert table.dtype == torch.uint8 and table.numel() == B * ctypes.sizeof(AugEntry)
-    out = torch.empty(B, 1, img_size, img_size, dtype=torch.float32, device=img_u8.device)
-    call("ym_augment_u8", img_u8.data_ptr(), meta.contiguous().data_ptr(), table.data_ptr(), B, img_size,
-         out.data_ptr(), stream_ptr(img_u8.device))
+    assert colour is None or (colour.dtype == torch.uint8 and colour.numel() == B * ctypes.sizeof(AugColour))
+    out = torch.empty(B, channels, img_size, img_size, dtype=torch.float32, device=img_u8.device)
+    if channels == 1 and colour is None:
+        call("ym_augment_u8", img_u8.data_ptr(), meta.contiguous().data_ptr(), table.data_ptr(), B, img_size,
+             out.data_ptr(), stream_ptr(img_u8.device))
+    else:
+        call("ym_augment_u8c", img_u8.data_ptr(), meta.contiguous().data_ptr(), table.data_ptr(), ptr(colour), B,
+             channels, img_size, out.data_ptr(), stream_ptr(img_u8.device))
     return out
 
 
 def table_bytes(entries) -> torch.Tensor:
-    """ctypes array of AugEntry -> host uint8 tensor (a copy)."""
+    """ctypes array of AugEntry (or AugColour) -> host uint8 tensor (a copy)."""
     return torch.from_numpy(np.frombuffer(bytes(entries), dtype=np.uint8).copy())
+
+
+def colour_table(hue, sat):
+    """Per-image hue shifts (turns) and saturation factors -> ctypes array of AugColour (Q16; the hue modulo one
+    turn, the factor clamped to [0, 2])."""
+    n = len(hue)
+    t = (AugColour * max(n, 1))()
+    for i in range(n):
+        t[i].hue = int(np.rint(np.float64(hue[i]) * 65536.0)) & 65535
+        t[i].sat = min(max(int(np.rint(np.float64(sat[i]) * 65536.0)), 0), 1 << 17)
+    return t
 
 
 class BatchAugment:
@@ -213,11 +241,21 @@ class BatchAugment:
         partners = torch.randint(0, max(B, 1), (B, 3), generator=g).numpy()
         mosaic_on = self.no_mosaic_from is None or epoch < self.no_mosaic_from
         sym = lambda col, r: (2.0 * u[:, col] - 1.0) * r        # noqa: E731  uniform(-r, r)
+        gain = 1.0 + (2.0 * torch.rand(B, generator=g, dtype=torch.float64).numpy() - 1.0) * h.gain
+        # hue and saturation are taken from the generator last: every other key is what it was before they existed
+        hs = 2.0 * torch.rand(B, 2, generator=g, dtype=torch.float64).numpy() - 1.0
         return {"mosaic": (u[:, 0] < h.mosaic) & mosaic_on, "cx": u[:, 1], "cy": u[:, 2], "partners": partners,
                 "angle": sym(3, h.degrees), "scale": 1.0 + sym(4, h.scale), "shear_x": sym(5, h.shear),
                 "shear_y": sym(6, h.shear), "tx": 0.5 + sym(7, h.translate), "ty": 0.5 + sym(8, h.translate),
-                "fliplr": u[:, 9] < h.fliplr, "flipud": u[:, 10] < h.flipud,
-                "gain": 1.0 + (2.0 * torch.rand(B, generator=g, dtype=torch.float64).numpy() - 1.0) * h.gain}
+                "fliplr": u[:, 9] < h.fliplr, "flipud": u[:, 10] < h.flipud, "gain": gain,
+                "hue": hs[:, 0] * h.hsv_h, "sat": 1.0 + hs[:, 1] * h.hsv_s}
+
+    def colours(self, B: int, epoch: int, step: int):
+        """The batch's ctypes table of AugColour, or None when hue and saturation are both off."""
+        if not (self.hyp.hsv_h or self.hyp.hsv_s):
+            return None
+        p = self.draw(B, epoch, step)
+        return colour_table(p["hue"], p["sat"])
 
     def plan(self, batch: dict, epoch: int, step: int):
         """Host side of one batch -> (ctypes table of AugEntry, batch_idx, cls, bboxes, max_gt)."""
@@ -272,9 +310,16 @@ class BatchAugment:
         if "img_u8" not in batch or self.hyp.is_off() or batch["img_meta"].shape[0] == 0:
             return prepare_batch(batch, device)              # synthetic batches carry no raw images
         table, bi, cl, bb, max_gt = self.plan(batch, epoch, step)
+        B, ch = int(batch["img_meta"].shape[0]), int(batch.get("img_ch", 1))
+        colour = self.colours(B, epoch, step) if ch == 3 else None
         tb = table_bytes(table)
+        n_table = tb.numel()                                    # B * 432: the colour table behind it is 8-byte aligned
+        if colour is not None:
+            tb = torch.cat((tb, table_bytes(colour)))           # one buffer, one transfer
         if torch.device(device).type == "cuda":
             tb = tb.pin_memory()
         mv = lambda t: t.to(device, non_blocking=True)          # noqa: E731
-        img = augment_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), mv(tb), int(batch["img_size"]))
+        tb = mv(tb)
+        img = augment_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), tb[:n_table], int(batch["img_size"]), ch,
+                            tb[n_table:] if colour is not None else None)
         return {"max_gt": max_gt, "img": img, "batch_idx": mv(bi), "cls": mv(cl), "bboxes": mv(bb)}

@@ -10,11 +10,13 @@ from __future__ import annotations
 import torch
 
 
-def collate_fn_cuda(batch, img_size=None):
+def collate_fn_cuda(batch, img_size=None, channels=1):
     """Batch dict of the reference collate (:289-346).  Images that are raw uint8 (1, h0, w0)
     (datasets.crater.CraterDatasetCUDA) are packed for the GPU resize instead of stacked:
     the dict then carries img_u8 / img_meta / img_size until datasets.prepare_batch moves it to
-    the device and produces img (B, 1, S, S) fp32."""
+    the device and produces img (B, 1, S, S) fp32.  `channels` > 1: the images are pixel-interleaved
+    (h0, w0, channels) (datasets.yolo_txt.YoloTxtDataset), the dict also carries img_ch and img is
+    (B, channels, S, S)."""
     imgs, boxes_list, labels_list, _ = zip(*batch)
     if imgs and imgs[0].dtype == torch.uint8:
         from .crater import pack_images
@@ -22,7 +24,7 @@ def collate_fn_cuda(batch, img_size=None):
         if size is None:
             raise ValueError("collate_fn_cuda: raw uint8 images need img_size (functools.partial(collate_fn_cuda, "
                              "img_size=S))")
-        out = pack_images(imgs, size)
+        out = pack_images(imgs, size, channels)
     else:
         out = {"img": torch.stack(imgs, 0)}
     bidx, cls, bboxes = [], [], []

@@ -112,30 +112,50 @@ class CraterDatasetCUDA(torch.utils.data.Dataset):
         return img, boxes, labels, idx
 
 
-def pack_images(imgs, img_size: int):
-    """Raw uint8 (1, h, w) images -> one pinned byte buffer + meta (B, 3) int64 {offset, h, w}."""
-    sizes = [int(t.shape[-2]) * int(t.shape[-1]) for t in imgs]
+def pack_images(imgs, img_size: int, channels: int = 1):
+    """Raw uint8 images -> one pinned byte buffer + meta (B, 3) int64 {offset, h, w}.  channels == 1: (1, h, w)
+    images; channels > 1: pixel-interleaved (h, w, channels) images, as the decoder yields them (offsets count
+    h * w * channels bytes), and the dict also carries "img_ch"."""
+    channels = int(channels)
+    if not 1 <= channels <= 4:
+        raise ValueError(f"pack_images: channels must be 1..4, got {channels}")
+    if channels > 1:
+        for t in imgs:
+            if t.dim() != 3 or int(t.shape[-1]) != channels:
+                raise ValueError(f"pack_images: expected (h, w, {channels}) uint8 images, got {tuple(t.shape)}")
+        hw = [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
+    else:
+        hw = [(int(t.shape[-2]), int(t.shape[-1])) for t in imgs]
+    sizes = [h * w * channels for h, w in hw]
     total = sum(sizes)
     buf = torch.empty(max(total, 1), dtype=torch.uint8)
     meta = torch.empty(len(imgs), 3, dtype=torch.int64)
     off = 0
     for i, (t, n) in enumerate(zip(imgs, sizes)):
         buf[off:off + n] = t.reshape(-1)
-        meta[i, 0], meta[i, 1], meta[i, 2] = off, int(t.shape[-2]), int(t.shape[-1])
+        meta[i, 0], meta[i, 1], meta[i, 2] = off, hw[i][0], hw[i][1]
         off += n
     if torch.cuda.is_available():
         buf, meta = buf.pin_memory(), meta.pin_memory()
-    return {"img_u8": buf, "img_meta": meta, "img_size": int(img_size)}
+    out = {"img_u8": buf, "img_meta": meta, "img_size": int(img_size)}
+    if channels > 1:
+        out["img_ch"] = channels
+    return out
 
 
-def resize_batch(img_u8: torch.Tensor, meta: torch.Tensor, img_size: int) -> torch.Tensor:
-    """GPU: packed uint8 images -> (B, 1, S, S) fp32 (ym_resize_linear_u8)."""
+def resize_batch(img_u8: torch.Tensor, meta: torch.Tensor, img_size: int, channels: int = 1) -> torch.Tensor:
+    """GPU: packed uint8 images -> (B, channels, S, S) fp32 (ym_resize_linear_u8; ym_resize_linear_u8c for
+    channels > 1, whose source is pixel-interleaved)."""
     from yolomi._lib import call, require_device, stream_ptr
     require_device(img_u8, meta)
     B = meta.shape[0]
-    out = torch.empty(B, 1, img_size, img_size, dtype=torch.float32, device=img_u8.device)
-    call("ym_resize_linear_u8", img_u8.data_ptr(), meta.contiguous().data_ptr(), B, img_size, out.data_ptr(),
-         stream_ptr(img_u8.device))
+    out = torch.empty(B, channels, img_size, img_size, dtype=torch.float32, device=img_u8.device)
+    if channels == 1:
+        call("ym_resize_linear_u8", img_u8.data_ptr(), meta.contiguous().data_ptr(), B, img_size, out.data_ptr(),
+             stream_ptr(img_u8.device))
+    else:
+        call("ym_resize_linear_u8c", img_u8.data_ptr(), meta.contiguous().data_ptr(), B, channels, img_size,
+             out.data_ptr(), stream_ptr(img_u8.device))
     return out
 
 
@@ -158,5 +178,5 @@ def prepare_batch(batch: dict, device) -> dict:
     for k, v in batch.items():
         out[k] = v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v
     if "img_u8" in out:
-        out["img"] = resize_batch(out.pop("img_u8"), out.pop("img_meta"), out.pop("img_size"))
+        out["img"] = resize_batch(out.pop("img_u8"), out.pop("img_meta"), out.pop("img_size"), out.pop("img_ch", 1))
     return out

@@ -276,13 +276,14 @@ def resume_checkpoint(path, model, optimizer, device, ema=None):
     return ckpt["epoch"] + 1, ckpt.get("best_loss", float("inf")), ckpt.get("best_mAP50", 0.0)
 
 
-def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None):
+def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None, channels=1):
     """The reference's split and loaders (:491-543): seed-42 permutation, Subset train / val,
     shuffled train loader, ordered val loader, drop_last=False.  Under data parallelism the train set
     is sharded by a DistributedSampler(shuffle=True, drop_last=True): every rank gets the same number
     of samples and so the same number of batches (a rank with one batch more would enter the gradient
     all-reduce alone and hang), reshuffled every epoch (set_epoch); the val set by ValShard (no
-    padding: no image counted twice).  -> (train_loader, val_loader, train_sampler or None)."""
+    padding: no image counted twice).  `channels`: the dataset's image planes, handed to the collate.
+    -> (train_loader, val_loader, train_sampler or None)."""
     import functools
     from torch.utils.data import DataLoader, DistributedSampler, Subset
     n = len(dataset)
@@ -290,7 +291,7 @@ def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate
     idx = torch.randperm(n, generator=torch.Generator().manual_seed(42)).tolist()
     tr, va = Subset(dataset, idx[: n - val_size]), Subset(dataset, idx[n - val_size:])
     nw = min(workers, 4)
-    col = collate or functools.partial(collate_fn, img_size=imgsz)
+    col = collate or functools.partial(collate_fn, img_size=imgsz, channels=channels)
     kw = dict(batch_size=batch, num_workers=nw, collate_fn=col, pin_memory=torch.cuda.is_available(),
               persistent_workers=nw > 0, prefetch_factor=2 if nw > 0 else None, drop_last=False)
     if dp_ctx is not None and dp_ctx.world > 1:
@@ -303,9 +304,9 @@ def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate
 
 
 class _SyntheticLoader:
-    def __init__(self, n, batch, imgsz, seed):
+    def __init__(self, n, batch, imgsz, seed, ch=1, nc=5):
         from datasets.synthetic import synth_batch
-        self._mk = lambda i: synth_batch(batch, imgsz, seed + i)
+        self._mk = lambda i: synth_batch(batch, imgsz, seed + i, nc=nc, ch=ch)
         self.n = n
 
     def __len__(self):
@@ -326,6 +327,13 @@ class _Parser(argparse.ArgumentParser):
                        "labels)")
         if ns.val_max_det < 0 or (ns.val_max_det and not ns.val_nms_per_class):
             self.error("--val-max-det N needs N >= 0 and --val-nms-per-class")
+        if ns.data_format == "crater" and ns.ch != 1:
+            self.error("--data-format crater reads single-plane images: --ch must be 1 (colour data: --data-format "
+                       "yolo)")
+        if ns.data_format == "yolo" and ns.ch not in (1, 3, 4):
+            self.error("--data-format yolo decodes to 1 (luma), 3 (RGB) or 4 (RGBA) planes")
+        if not 1 <= ns.ch <= 4 or ns.nc < 1:
+            self.error("--ch is 1..4 and --nc at least 1")
         return ns, rest
 
 
@@ -347,6 +355,11 @@ def build_parser():
     ap.add_argument("--max-val-batches", type=int, default=None)
     ap.add_argument("--val-conf", type=float, default=0.25)
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic batches (no dataset needed)")
+    ap.add_argument("--data-format", type=str, default="crater", choices=["crater", "yolo"],
+                    help="crater: the CSV + grayscale crater layout; yolo: images/ + labels/<stem>.txt with rows "
+                         "`cls cx cy w h` normalised (datasets/yolo_txt.py)")
+    ap.add_argument("--ch", type=int, default=1, help="image planes: 1 (luma), 3 (RGB) or 4 (RGBA); crater data is 1")
+    ap.add_argument("--nc", type=int, default=5, help="number of classes")
     ap.add_argument("--augment", action="store_true", help="GPU training augmentation (datasets/augment.py)")
     ap.add_argument("--mosaic", type=float, default=1.0, help="probability of a 4-tile mosaic")
     ap.add_argument("--degrees", type=float, default=0.0, help="rotation range (+/- degrees)")
@@ -357,6 +370,10 @@ def build_parser():
     ap.add_argument("--fliplr", type=float, default=0.5, help="probability of a left-right flip")
     ap.add_argument("--flipud", type=float, default=0.0, help="probability of an up-down flip")
     ap.add_argument("--gain", type=float, default=0.4, help="value gain range (+/- fraction; Ultralytics' hsv_v)")
+    ap.add_argument("--hsv-h", type=float, default=0.015, help="hue shift range (+/- fraction of a turn); used with "
+                    "--augment on 3-plane data only")
+    ap.add_argument("--hsv-s", type=float, default=0.7, help="saturation factor range (+/- fraction around 1); used "
+                    "with --augment on 3-plane data only")
     ap.add_argument("--close-mosaic", type=int, default=10, help="no mosaic in the last N epochs")
     ap.add_argument("--aug-seed", type=int, default=0)
     ap.add_argument("--val-per-class", action="store_true",
@@ -390,20 +407,25 @@ def main():
 
     if args.synthetic:
         seed = 1000 * (dp_ctx.rank if dp_ctx else 0)
-        train_loader = _SyntheticLoader(args.synthetic, args.batch, args.imgsz, seed)
-        val_loader = _SyntheticLoader(max(1, args.synthetic // 5), args.batch, args.imgsz, seed + 10 ** 6)
+        train_loader = _SyntheticLoader(args.synthetic, args.batch, args.imgsz, seed, args.ch, args.nc)
+        val_loader = _SyntheticLoader(max(1, args.synthetic // 5), args.batch, args.imgsz, seed + 10 ** 6, args.ch,
+                                      args.nc)
         train_sampler = None
     else:
-        from datasets import CraterDatasetCUDA
-        dataset = CraterDatasetCUDA(args.data, img_size=args.imgsz, cache_images=False, augment=True)
+        if args.data_format == "yolo":
+            from datasets import YoloTxtDataset
+            dataset = YoloTxtDataset(args.data, img_size=args.imgsz, channels=args.ch, cache_images=False)
+        else:
+            from datasets import CraterDatasetCUDA
+            dataset = CraterDatasetCUDA(args.data, img_size=args.imgsz, cache_images=False, augment=True)
         train_loader, val_loader, train_sampler = make_loaders(dataset, args.val_split, args.batch, args.workers,
-                                                               args.imgsz, dp_ctx)
+                                                               args.imgsz, dp_ctx, channels=args.ch)
 
     import yaml
     with open(args.cfg) as f:
         cfg_dict = yaml.safe_load(f)
     cfg_dict["scale"] = args.scale
-    model = build_yolo11(cfg=cfg_dict, ch=1, nc=5).to(device)
+    model = build_yolo11(cfg=cfg_dict, ch=args.ch, nc=args.nc).to(device)
     if rank0:
         n_params = sum(p.numel() for p in model.parameters())
         print(f"Total parameters: {n_params:,} ({n_params / 1e6:.2f}M)")
@@ -436,7 +458,8 @@ def main():
     if args.augment:
         from datasets import AugmentHyp, BatchAugment
         hyp = AugmentHyp(mosaic=args.mosaic, degrees=args.degrees, translate=args.translate, scale=args.aug_scale,
-                         shear=args.shear, fliplr=args.fliplr, flipud=args.flipud, gain=args.gain)
+                         shear=args.shear, fliplr=args.fliplr, flipud=args.flipud, gain=args.gain,
+                         hsv_h=args.hsv_h if args.ch == 3 else 0.0, hsv_s=args.hsv_s if args.ch == 3 else 0.0)
         # train_one_epoch counts epochs from 1: the last `close_mosaic` of them draw no mosaic
         augment = BatchAugment(hyp, seed=args.aug_seed, rank=dp_ctx.rank if dp_ctx else 0,
                                no_mosaic_from=args.epochs - args.close_mosaic + 1)

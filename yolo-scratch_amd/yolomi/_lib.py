@@ -67,6 +67,11 @@ class AugEntry(ctypes.Structure):
                 ("flags", I32), ("reserved", I32)]
 
 
+class AugColour(ctypes.Structure):
+    """ym_aug_colour (include/yolomi.h): per-image hue shift and saturation factor, Q16."""
+    _fields_ = [("hue", I32), ("sat", I32)]
+
+
 R = _c.c_int
 # name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (its YM_EXPERIMENTS block
 # excepted: the measurement library's)
@@ -172,6 +177,8 @@ SIGNATURES = {
     "ym_iou_matrix": (R, [P, P, I64, I64, P, P]),
     "ym_resize_linear_u8": (R, [P, P, INT, INT, P, P]),
     "ym_augment_u8": (R, [P, P, P, INT, INT, P, P]),
+    "ym_resize_linear_u8c": (R, [P, P, INT, INT, INT, P, P]),
+    "ym_augment_u8c": (R, [P, P, P, P, INT, INT, INT, P, P]),
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),
