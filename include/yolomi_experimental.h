@@ -83,35 +83,6 @@ int ym_conv_set_eval_gemm_tiles(int max_tiles);
  * like ym_conv_set_halo. */
 int ym_bn_set_bwd_fold(int mode);
 
-#ifdef YM_EXPERIMENTS
-/* Measurement library only (make -C yolo-scratch_amd/csrc exp -> libyolomi_exp.so; NOT exported by libyolomi.so):
- * conv_pipe experiment instances — 1 the 8-wave 256x128 tile, 10-13 ablations that skip DMAs or MFMAs (WRONG results
- * by design, for timing only), 20 the generic control path.  0 restores the shipped kernels. */
-int ym_pipe_set_exp(int v);
-/* MFMA shape of the persistent pipelined implicit GEMM (round 6, measured slower: profiles/r06/pipe_mfma_order_ab.txt):
- * 0 (default) v_mfma_f32_16x16x32 on the shipped tiles, 1 v_mfma_f32_32x32x16 on the same tiles, 2 v_mfma_f32_32x32x16 with the 256 x 128 tile on 8 waves of 64 x 64 instead
- * of 16 of 32 x 64.  Returns the previous setting. */
-int ym_conv_set_pipe_mfma(int mode);
-/* K-step issue order of the pipelined kernels (round 6, measured slower: profiles/r06/pipe_mfma_order_ab.txt):
- * 0 (default) stage DMAs first after the barrier, the next stage's fragment reads late; 1 every fragment read pinned ahead of the half step of MFMAs it covers.  Returns the
- * previous setting. */
-int ym_conv_set_pipe_order(int mode);
-/* Loop form of the pipelined kernel's single-class training instances (round 6): 0 one flat loop over the workgroup's K
- * steps, 1 nested tiles x K steps with each tile's first step peeled, 2 (default, shipped) as 1 with the LDS ring slot
- * carried as a byte offset.  Out of range restores 2.  Returns the previous setting. */
-int ym_conv_set_pipe_loop(int mode);
-/* Tap lookahead of the 3x3 weight-gradient kernel (round 6): 0 each tap's input fragments read right before its MFMAs,
- * 1 one tap ahead.  Out of range restores the shipped setting.  Returns the previous setting. */
-int ym_wgrad_set_lookahead(int la);
-/* K order of the pipelined kernel's single-class forward (round 6): 0 channel chunk innermost everywhere, 1 tap
- * innermost everywhere (the taps that re-read the same input pixels back to back), anything else (default) the shipped
- * rule — tap innermost on the stride-2 3x3 forwards reading maps >= 128 wide.  Returns the previous setting. */
-int ym_conv_set_pipe_taporder(int mode);
-/* Loop form of the pipelined kernel's eval instance (round 6): 2 the nested form the training instances ship, anything
- * else (default) the flat loop.  Returns the previous setting. */
-int ym_conv_set_pipe_eval_loop(int mode);
-#endif
-
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,6 @@ def declared(header=None):
     names = set()
     for h in ([header] if header else HEADERS):
         txt = (ROOT / "include" / h).read_text()
-        # the measurement library's block (libyolomi_exp.so only) is not part of the shipping ABI
-        txt = re.sub(r"#ifdef YM_EXPERIMENTS.*?#endif", "", txt, flags=re.S)
         names |= set(re.findall(r"^\s*(?:const\s+|unsigned\s+)?[\w\s\*]+?\b(ym_\w+)\s*\(", txt, re.M))
     return sorted(names)
 
@@ -36,8 +34,8 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_library_exports_nothing_undeclared():
-    """The shipping library's dynamic ym_ symbols are exactly the declared ones: no experiment hook (ym_pipe_set_exp
-    and the ablation instances are built into libyolomi_exp.so only) and no stray helper."""
+    """The shipping library's dynamic ym_ symbols are exactly the declared ones: no hook for an experiment the
+    headers do not declare and no stray helper."""
     out = subprocess.run(["nm", "-D", "--defined-only", str(PKG / "libyolomi.so")], capture_output=True, text=True,
                          check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("ym_")}

@@ -198,14 +198,17 @@ PIPE = [
     (70, 63, 61, 128, 128, 3, 2, 1, 0, 0),     # odd map: unequal stride-2 classes (class-major tile order)
     (16, 64, 64, 256, 128, 1, 1, 0, 128, 0),
     (12, 80, 80, 64, 64, 3, 1, 1, 0, 0),
+    # the 256 x 64 tile's tap-innermost forward (stride 2, input map >= 128 wide, < 128 output channels) and its
+    # four-class data gradient; 256 tiles: exactly the ym_conv_set_pipe(2) threshold
+    (16, 128, 128, 64, 64, 3, 2, 1, 0, 0),
 ]
 
 
 @pytest.mark.parametrize("shape", PIPE, ids=[f"n{s[0]}h{s[1]}w{s[2]}c{s[3]}o{s[4]}k{s[5]}s{s[6]}" for s in PIPE])
 def test_pipe_kernel_vs_torch(shape):
     """fp16 forward (+ BN statistic partials), bf16 data gradient (overwrite, then accumulate).  (The round-6
-    32x32x16-MFMA and reads-first variants, measurement library only, passed this test on every shape:
-    profiles/r06/pytest_pipe_variants.log.)"""
+    32x32x16-MFMA and reads-first variants, measured and rejected, passed this test on every shape of that time:
+    profiles/r06/pytest_pipe_variants.log; their code is in history at the parent of the commit that removed them.)"""
     from yolomi._lib import lib
     _views_fwd_dgrad_check(shape, lib().ym_conv_set_pipe, 2, 2)
 

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--halo", type=int, default=-1, help="ym_conv_set_halo policy for this run (A/B)")
     ap.add_argument("--direct", type=int, default=-1, help="ym_conv_set_direct policy for this run (A/B)")
     ap.add_argument("--set", nargs="*", default=[], help="other library setters for this run, NAME=VALUE "
-                                                        "(e.g. ym_pipe_set_exp=1)")
+                                                        "(e.g. ym_conv_set_fold=0)")
     ap.add_argument("--names", action="store_true", help="append each launch's kernel instance (ym_conv_kernel)")
     ap.add_argument("--seq-out", help="counter-pass mode: write the (op, kind, k, flops, launches) order of the "
                                       "timed groups here and separate the groups with a marker kernel "

@@ -1,5 +1,5 @@
-"""Same-process A/B of an experimental conv_pipe configuration switch (an extern "C" setter that is NOT in
-the header) on the s@640 bs64 plan's layers, variants interleaved over rounds.
+"""Same-process A/B of a library policy (any exported extern "C" setter, e.g. ym_conv_set_pipe; YOLOMI_LIB picks another
+build of the library) on the s@640 bs64 plan's layers, variants interleaved over rounds.
 usage: python tools/pipe_ab.py SETTER --only 6 10 34 --variants 0 1
        python tools/pipe_ab.py SETTER --setter2 SETTER2 --variants 0:0 0:1 2:1   (value pairs for two setters)
 """

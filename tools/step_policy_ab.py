@@ -1,9 +1,9 @@
-"""In-step A/B of an experimental library policy (an extern "C" setter of yolomi_experimental.h; run with
-YOLOMI_LIB=.../libyolomi_exp.so): the s@640 bs64 training step (forward + fused loss + backward + FusedAdamW) timed
+"""In-step A/B of a library policy (an extern "C" setter of yolomi_experimental.h, or any setter another build of the
+library exports: YOLOMI_LIB picks the build): the s@640 bs64 training step (forward + fused loss + backward + FusedAdamW) timed
 per variant, variants interleaved over rounds in one process (cdna_hip_programming.md §5.4 rule 24).  Measurement
 only, never a bench number.
 
-usage: YOLOMI_LIB=$PWD/yolo-scratch_amd/libyolomi_exp.so python tools/step_policy_ab.py SETTER --variants 0 1
+usage: python tools/step_policy_ab.py SETTER --variants 0 1
 """
 import argparse
 import statistics

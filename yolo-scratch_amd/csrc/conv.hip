@@ -64,34 +64,11 @@ struct GemmArgs {
     BnFoldArgs fold;                         // BatchNorm finalize as the tail (ym_conv_fwd_bn); gamma null = off
 };
 
-// LDS images are lane-linear (LDS-DMA writes lane l of a wave-instruction at base + 16*l): 128-B
-// rows of 8 16-B slots, row r's chunk c stored in slot c ^ f(r), f(r) = (r >> 1) & 7.  The swizzle
-// lives on the global (source) side: a DMA lane that fills slot s of row r loads chunk s ^ f(r), so
-// each 8-lane group still reads one whole 128-B row.  A ds_read_b128 lane group (rows {0-3,12-15}
-// at chunk c, rows {4-11} at chunk c^1) then covers 16 distinct (row parity, slot) bank quads.
-// 64-B rows (32-deep K stages, 4 slots): slot c ^ F(r), F(r) = 2 * ((r >> 2) & 1) — measured
-// conflict-free (SQ_LDS_BANK_CONFLICT 0; the earlier F = {0, 3, 2, 1}[(r >> 2) & 3] cost 45-50 %
-// extra LDS cycles in the 128x64 tiles, tools/pmc_conv.sh).
+// LDS row swizzle by row width (tile.h: fsw128 for 64-deep K stages, fsw64 for 32-deep ones)
 template <int RB>
 __device__ __forceinline__ int fsw(int r) {
-    if constexpr (RB == 128) return (r >> 1) & 7;
-    else return ((r >> 2) & 1) << 1;                    // F(r) = 2 * ((r >> 2) & 1)
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-    asm volatile("" ::: "memory");
-}
-
-// workgroup barrier without the vmcnt(0) drain __syncthreads() implies; LDS-DMA ordering is
-// the caller's (counted wait_vmcnt before it), the asm clobbers keep LDS accesses on their side
-__device__ __forceinline__ void raw_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    if constexpr (RB == 128) return fsw128(r);
+    else return fsw64(r);
 }
 
 // WM x WN waves: wave (wr, wc) owns BN/WM channels x BM/WN pixels of the tile; KB-deep K stages
@@ -278,9 +255,9 @@ conv_gemm_kernel(GemmArgs a, EvalArgs e) {
             const int buf = k % NSTAGE;
             // this wave's DMAs of stage k have landed (the later stages may stay in flight)
             const int ahead = min(NSTAGE - 2, nkl - 1 - k);
-            if (NSTAGE >= 4 && ahead >= 2) wait_vmcnt<(NSTAGE >= 4 ? 2 : 0) * (AI + BI)>();
-            else if (NSTAGE >= 3 && ahead >= 1) wait_vmcnt<(NSTAGE >= 3 ? 1 : 0) * (AI + BI)>();
-            else wait_vmcnt<0>();
+            if (NSTAGE >= 4 && ahead >= 2) vm_wait<(NSTAGE >= 4 ? 2 : 0) * (AI + BI)>();
+            else if (NSTAGE >= 3 && ahead >= 1) vm_wait<(NSTAGE >= 3 ? 1 : 0) * (AI + BI)>();
+            else vm_wait<0>();
             raw_barrier();                 // ... everyone's, and everyone finished reading stage k-1
             if (k + NSTAGE - 1 < nkl) issue((k + NSTAGE - 1) % NSTAGE);
             const char* As = smem + buf * STAGE;

@@ -13,7 +13,7 @@
 // K loop: steps k = (32-channel chunk cc, kernel row kh), each step = the row's 3 taps.  LDS: two halo images (chunk cc and cc+1) and an
 // NW-deep ring of weight slices, all filled by LDS-DMA (buffer_load ... lds) with source-side
 // swizzle, counted vmcnt waits (the halo of the next chunk and NW-2 weight slices stay in flight)
-// and raw barriers.  64-B LDS rows (32 channels): row r's 16-B chunk c lives in slot c ^ F(r) (fsw64 below).
+// and raw barriers.  64-B LDS rows (32 channels): row r's 16-B chunk c lives in slot c ^ F(r) (tile.h fsw64).
 // Pixels of a fragment map to halo rows through a per-lane base (row-major tile, any TW), so tile
 // rectangles need not be powers of two (40x40 maps use 40 x 6 tiles); pixels past the map edge are
 // computed on zero-padded halo rows and masked in the epilogue.
@@ -49,42 +49,15 @@ struct HaloArgs {
     BnFoldArgs fold;                          // BatchNorm finalize as the tail (ym_conv_fwd_bn); gamma null = off
 };
 
-// 64-B LDS rows (32 channels): row r's 16-B chunk c lives in slot c ^ F(r), F(r) = 2 * ((r >> 2) & 1).
-// A ds_read_b128 lane group reads 16 rows s + fr at chunks c (fr in {0-3, 12-15}) and c ^ 1
-// (fr in {4-11}) (or the reverse); rows s+k, s+k+4, s+k+8, s+k+12 share bank quads and land on
-// chunks {c, c^3, c^1, c^2} for EVERY start s — the halo fragments start at arbitrary rows (tap
-// shifts, tile rows), where the earlier F = {0,3,2,1}[(r>>2)&3] conflicted 1.8-2.4x
-// (bank-conflict model over the kernel's fragment rows: 7.3-9.4 LDS cycles per read -> 4.0-6.4).
-__device__ __forceinline__ int fsw64(int r) { return ((r >> 2) & 1) << 1; }
-
-// one 1-KiB LDS-DMA piece: lane l's 16 bytes from rsrc + voff + soff land at lds + 16 l.  (A function, not the builtin
-// written inline in the kernel's lambdas: there hipcc's host pass silently dropped the kernels' launch stubs.)
-__device__ __forceinline__ void dma16h(__amdgpu_buffer_rsrc_t r, char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-    asm volatile("" ::: "memory");
-}
 // wave-uniform count -> immediate: waits until at most n of this wave's vector-memory ops are pending
 template <int MAXN>
 __device__ __forceinline__ void wait_vm_dyn(int n) {
     if constexpr (MAXN == 0) {
-        wait_vm<0>();
+        vm_wait<0>();
     } else {
-        if (n >= MAXN) wait_vm<MAXN>();
+        if (n >= MAXN) vm_wait<MAXN>();
         else wait_vm_dyn<MAXN - 1>(n);
     }
-}
-
-__device__ __forceinline__ void raw_barrier() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 // WPX x WCO waves; wave tile TPW x 16 pixels by TCW x 16 channels; HI halo DMA instructions per
@@ -185,11 +158,11 @@ conv_halo_kernel(HaloArgs a, EvalArgs e) {
             if (cc == k_tail) {
 #pragma unroll
                 for (int j = 0; j < HI; ++j)
-                    dma16h(xres, dst + (wave * HI + j) * 1024, cc * 32 + h_ch[j] < a.Kin ? h_off[j] : OOB, uint32_t(cc) * 64u);
+                    dma16(xres, dst + (wave * HI + j) * 1024, cc * 32 + h_ch[j] < a.Kin ? h_off[j] : OOB, uint32_t(cc) * 64u);
                 return;
             }
 #pragma unroll
-            for (int j = 0; j < HI; ++j) dma16h(xres, dst + (wave * HI + j) * 1024, h_off[j], uint32_t(cc) * 64u);
+            for (int j = 0; j < HI; ++j) dma16(xres, dst + (wave * HI + j) * 1024, h_off[j], uint32_t(cc) * 64u);
         };
         // weight stream position (step k's chunk / kernel row / ring slot), advanced per issued step
         int w_cc = 0, w_kh = 0, w_slot = 0;
@@ -199,10 +172,10 @@ conv_halo_kernel(HaloArgs a, EvalArgs e) {
             if (w_cc == k_tail) {
 #pragma unroll
                 for (int j = 0; j < WI; ++j)
-                    dma16h(wres, dst + (wave * WI + j) * 1024, w_cc * 32 + a_ch[j] < a.Kin ? a_off[j] : OOB, soff);
+                    dma16(wres, dst + (wave * WI + j) * 1024, w_cc * 32 + a_ch[j] < a.Kin ? a_off[j] : OOB, soff);
             } else {
 #pragma unroll
-                for (int j = 0; j < WI; ++j) dma16h(wres, dst + (wave * WI + j) * 1024, a_off[j], soff);
+                for (int j = 0; j < WI; ++j) dma16(wres, dst + (wave * WI + j) * 1024, a_off[j], soff);
             }
             if (++w_kh == 3) { w_kh = 0; ++w_cc; }
             w_slot = w_slot == NW - 1 ? 0 : w_slot + 1;
@@ -374,7 +347,7 @@ conv_halo_kernel(HaloArgs a, EvalArgs e) {
 
     if (a.st_sum) {
         float (*red)[WPX][BN] = reinterpret_cast<float (*)[WPX][BN]>(smem);   // [sum|sq][pixel wave][channel]
-        wait_vm<0>();
+        vm_wait<0>();
         raw_barrier();                    // staging LDS is free again
 #pragma unroll
         for (int i = 0; i < TCW; ++i)

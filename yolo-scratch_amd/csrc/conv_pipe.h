@@ -16,10 +16,6 @@ struct PipePlan {
 
 // pol.pipe: -1 default policy (3); 0 never; 1 layers of >= 1024 tiles, >= 128 channels; 2 >= 256
 // tiles; 3 the wider rule of pipe_plan (ym_conv_set_pipe)
-#ifdef YM_EXPERIMENTS
-int pipe_order_exp();     // K-step issue order of the pipelined kernels (conv_pipe / conv_hpipe RO; measurement only)
-#endif
-
 // dgrad = 0: forward conv described by d; 1: its data gradient
 PipePlan pipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol);
 // fold: the BatchNorm finalize as the launch's tail (ym_conv_fwd_bn; forward with statistics only) or null

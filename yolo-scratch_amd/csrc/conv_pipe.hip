@@ -40,24 +40,18 @@ namespace ym {
 // selection policy (ym_conv_set_pipe): -1 default (3); 0 never; 1 layers of >= 1024 tiles with >= 128
 // output channels, no stride-2 data gradient; 2 every eligible layer of >= 256 tiles; 3 (default) the
 // wider rule of pipe_plan (s@640 bs64 step: 2940 img/s vs 2902 for rule 1)
-// experiments (ym_pipe_set_exp, yolomi_experimental.h; tools/pipe_ab.py): 0 shipped; 1 the 8-wave 256 x 128 tile;
-// 10-13 ablations of the 16-wave tile (conv_pipe_kernel ABL 1, 2, 4, 8: wrong results by design); 20 the generic
-// (class-search) control path.  Built only into the measurement library (make exp: -DYM_EXPERIMENTS,
-// libyolomi_exp.so); the shipping libyolomi.so has neither the setter nor the ablation instances.
-// Measured and rejected in round 6, built into the measurement library only (profiles/r06/pipe_mfma_order_ab.txt):
-// the MFMA shape (ym_conv_set_pipe_mfma: 0 16x16x32 shipped; 1 32x32x16 on the same tiles, +8..+23 % per layer;
-// 2 32x32x16 on 8 waves of 64 x 64, +1..+14 %) and the K-step issue order (ym_conv_set_pipe_order / conv_pipe_kernel
-// RO: 1 pins every fragment read ahead of the MFMAs it covers, -3..+7 %)
-#ifdef YM_EXPERIMENTS
-Policy g_pipe_mfma{0};
-Policy g_pipe_order{0};   // also conv_hpipe.hip (pipe_order_exp)
-Policy g_pipe_loop{2};    // conv_pipe_kernel LP of the single-class path (2 shipped)
-Policy g_pipe_eval_loop{0};  // conv_pipe_kernel LP of the eval instance (0 shipped, 2 the nested loop)
-Policy g_pipe_taporder{-1};  // conv_pipe_kernel TO of the single-class forward: -1 the shipped rule (tap_inner), 0 / 1 forced
-Policy g_pipe_exp{0};
-#else
-constexpr int g_pipe_exp = 0;
-#endif
+//
+// Measured and rejected, with the profile that holds the numbers (the code of every variant is in history at the parent
+// of the commit that removed them, where a second build of the library carried them behind setters):
+//  * 256 x 128 on 8 waves of 64 x 64 for training: within +-3.5 % of the 16-wave tile (profiles/r05/pipe_wave_tile_ab.txt);
+//  * the 32x32x16 MFMA shape, on the same tiles +8..+23 % per layer, on 8 waves of 64 x 64 +1..+14 %, and every fragment
+//    read pinned ahead of the MFMAs it covers, -3..+7 % (profiles/r06/pipe_mfma_order_ab.txt);
+//  * the nested loop without the carried slot offset (profiles/r06/pipe_loop_ab.txt), the nested loop for the eval
+//    instance (profiles/r06/pipe_eval_loop_ab.txt), tap-innermost K order everywhere (profiles/r06/pipe_taporder_ab.txt);
+//  * the LDS-transposed epilogue, 2-7 % slower on every forward (profiles/r04/pipe_fwd_reg_epilogue_ab.txt);
+//  * the ablation instances (no DMA / no MFMA / one operand's DMA only; wrong results by design) that located the time
+//    (profiles/r05/pipe_ablation_ab.txt) and the class-search control path forced everywhere
+//    (profiles/r05/pipe_c1_vs_generic_ab.txt).
 
 namespace {
 
@@ -109,8 +103,6 @@ __device__ __forceinline__ int cls_find(const PipeArgs& a, int mt) {
     return c;
 }
 
-__device__ __forceinline__ int fsw128(int r) { return (r >> 1) & 7; }
-
 // (image, in-image index, row) of pixel m0 + r, r < 256, given the tile's (tn, tp) = divmod(m0, ohw) (computed
 // once per tile): one wrap for the image, the row by the float reciprocal of the row width with one
 // correction (x < 2^24) — the generic 32-bit divisions these replace cost ~30 VALU each and ran per pixel
@@ -126,32 +118,6 @@ __device__ __forceinline__ void split_pix(uint32_t tn, uint32_t tp, uint32_t r, 
     row = q;
 }
 
-// one 1-KiB LDS-DMA piece: lane l's 16 bytes from rsrc + voff + soff land at lds + 16 l
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, char* lds, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-    asm volatile("" ::: "memory");
-}
-
-// every ds_read issued so far has returned, then the workgroup barrier (no vmcnt drain); the
-// sched_barriers keep the compiler from moving MFMAs / LDS reads across it
-__device__ __forceinline__ void step_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    // the builtin, not inline asm: the compiler's wait-count pass sees this wait, so the MFMAs after the
-    // barrier do not wait again for the fragments read before it (with an asm wait they stalled on the
-    // next stage's freshly issued reads: lgkmcnt(3..0) ahead of the first four MFMAs of every step)
-    __builtin_amdgcn_s_waitcnt(0xC07F);       // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // issue side of the stage stream: which tile / tap / 64-channel chunk the next LDS-DMA stage
 // stages, and the per-lane gather offsets of the current tile and tap.  All control state is
 // wave-uniform (scalar registers); per stage the DMAs cost one M0 write each, per tap one
@@ -165,7 +131,7 @@ __device__ __forceinline__ void step_barrier() {
 // (tap 0, chunk 1), .., (tap 1, chunk 0), ..; 1: tap innermost — every tap of channel chunk 0, then of chunk 1, so
 // the taps that re-read the same input pixels run back to back and their overlap comes from L2 (one 64-channel
 // chunk's footprint per tile instead of every chunk's)
-template <int BM, int BN, int NW, int MODE, int ABL = 0, bool C1 = false, int TO = 0>
+template <int BM, int BN, int NW, int MODE, bool C1 = false, int TO = 0>
 struct Issuer {
     static constexpr int AI = BN / 8 / NW, BI = BM / 8 / NW, RB = 128;
     const PipeArgs& a;
@@ -323,10 +289,10 @@ struct Issuer {
         }
 #pragma unroll
         for (int j = 0; j < AI; ++j)
-            dma16(wres, st + (wave * AI + j) * 1024, live && !(ABL & 9) ? a_off[j] : OOB, a_tap + kb);
+            dma16(wres, st + (wave * AI + j) * 1024, live ? a_off[j] : OOB, a_tap + kb);
 #pragma unroll
         for (int j = 0; j < BI; ++j)
-            dma16(xres, st + BN * RB + (wave * BI + j) * 1024, live && !(ABL & 5) ? b_off[j] : OOB, kb);
+            dma16(xres, st + BN * RB + (wave * BI + j) * 1024, live ? b_off[j] : OOB, kb);
     }
 
     // advance the stream position by one stage (new tap: its gather offsets; new tile: its pixels)
@@ -374,55 +340,38 @@ struct Issuer {
     }
 };
 
-// EPI 2: the register-only epilogue (epilogue_regs: no LDS, so hipcc does not drain the in-flight stages in front of
-// it) whose stores the next step's wait leaves in flight — both directions since round 4 (the LDS-transposed form
-// measured 2-7 % slower on every forward, profiles/r04/pipe_fwd_reg_epilogue_ab.txt)
-// ABL (ablations for measurement only, never selected by pipe_plan): 1 every stage DMA out of range (issued, nothing
-// fetched), 2 no MFMAs (fragments still read), 4 only the gathered input's DMAs out of range, 8 only the weights'
+// The epilogue is register-only (conv_epi.h epilogue_regs: no LDS, so hipcc does not drain the in-flight stages in front
+// of it) and the next step's wait leaves its stores in flight — both directions since round 4.
 // C1: one output class on maps of >= BM pixels (Issuer's fast path; the stride-2 data gradient's four classes and tiny
 // maps take the generic one)
 // EV: the eval-mode Conv block instance (ym_conv_fwd_eval at large batches: running-statistics BatchNorm / SiLU /
 // residual in the register epilogue, conv_epi.h EvalEpi; a C1 forward without statistics; e is not read otherwise)
-// MF: the MFMA shape — 16 (v_mfma_f32_16x16x32: 16x16 subtiles, one MFMA per 32-deep half and subtile pair) or 32
-// (v_mfma_f32_32x32x16, round 6: 32x32 subtiles, two 16-deep MFMAs per half; half the MFMA instructions for the same
-// FLOPs, a 32-cycle issue window per MFMA instead of 16, the same LDS fragment bytes; conv_epi.h epilogue_regs32_x)
-// RO: issue order inside a K step (round 6).  0: after the barrier the stage DMAs go out between the second half's MFMAs
-// and the next stage's first-half fragments are read two MFMAs before the end of the step (the compiler also floats the
-// second-half reads into the middle of the first half); 1: every fragment read is pinned ahead of the MFMAs it covers —
-// the second-half reads at the top of the step, the next stage's first-half reads right after the barrier, ahead of
-// the DMAs — so each read has a whole half (TM * TN * KS MFMAs per wave) of cover
-// LP: loop form of the single-class path (round 6).  0: one flat loop over the workgroup's K steps whose body tests for
-// a tile's first step (accumulator reset, the wait that leaves the previous epilogue's stores in flight) and last step
-// (epilogue) every iteration; 1: tiles x K steps as two nested loops — the tile's first step peeled with its own wait,
-// the inner loop a bare K step; 2 (shipped for the training instances since round 6): as 1 with the ring slot carried as
-// a byte offset (an add instead of a multiply) and the stream-end test against a hoisted limit.  ~22 instead of ~33
-// scalar instructions per common K step; same-process layer A/B (profiles/r06/pipe_loop_ab.txt) -1..-5 % on most
-// pipelined layers (op 71 fwd -11.6 %), op 73 fwd +1.5 %; the whole step within +-0.2 % (the launches overlap other
-// streams' work there).  The eval instance keeps 0 (not measured)
-template <int BM, int BN, int WM, int WN, int MODE, int EPI = 2, int NS = 3, int ABL = 0, bool C1 = false,
-          bool EV = false, int MF = 16, int RO = 0, int LP = 0, int TO = 0>
+// NESTED: loop form.  false (the generic and eval instances): one flat loop over the workgroup's K steps whose body tests
+// for a tile's first step (accumulator reset, the wait that leaves the previous epilogue's stores in flight) and last
+// step (epilogue) every iteration; true (the C1 training instances since round 6): tiles x K steps as two nested loops —
+// the tile's first step peeled with its own wait, the inner loop a bare K step, the ring slot carried as a byte offset
+// (an add instead of a multiply) and the stream-end test against a hoisted limit.  ~22 instead of ~33 scalar
+// instructions per common K step; same-process layer A/B (profiles/r06/pipe_loop_ab.txt) -1..-5 % on most pipelined
+// layers (op 71 fwd -11.6 %), op 73 fwd +1.5 %; the whole step within +-0.2 % (the launches overlap other streams' work
+// there).  The eval instance measured within the run-to-run spread either way (profiles/r06/pipe_eval_loop_ab.txt)
+// TO: Issuer's K order (tap_inner decides where it is 1)
+template <int BM, int BN, int WM, int WN, int MODE, bool C1 = false, bool EV = false, bool NESTED = false, int TO = 0>
 __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, EvalArgs e) {
-    static_assert(!EV || (C1 && MODE == PF && ABL == 0), "the eval instance is a single-class forward");
-    static_assert(MF == 16 || MF == 32, "MFMA shape");
-    // NS: LDS ring of K stages — stage g computing, g+1 .. g+NS-1 in flight (3; 2 for the 64-KB+ stages of the
-    // 256-channel / 512-pixel tiles)
-    static_assert(NS == 2 || NS == 3, "ring depth");
-    static_assert(LP == 0 || C1, "the nested loop form is the single-class path's");
+    static_assert(!EV || (C1 && MODE == PF), "the eval instance is a single-class forward");
+    static_assert(!NESTED || C1, "the nested loop form is the single-class path's");
+    // LDS ring of K stages — stage g computing, g+1 .. g+NS-1 in flight
+    constexpr int NS = 3;
     constexpr int RB = 128;                   // 64 K x 2 B per LDS row
     constexpr int NW = WM * WN;
     constexpr int AI = BN / 8 / NW;           // weight DMA instructions per wave per stage
     constexpr int BI = BM / 8 / NW;           // activation DMA instructions per wave per stage
     constexpr int DPS = AI + BI;              // DMAs per wave per stage (the vmcnt unit)
-    constexpr int TM = BN / WM / MF;          // MF-channel subtiles per wave
-    constexpr int TN = BM / WN / MF;          // MF-pixel subtiles per wave
-    constexpr int KS = MF == 16 ? 1 : 2;      // MFMA K slices per 32-deep half (and fragment reads per subtile)
-    constexpr int NR = MF == 16 ? 4 : 16;     // accumulator registers per subtile and lane
-    typedef float AccT __attribute__((ext_vector_type(NR)));
+    constexpr int TM = BN / WM / 16;          // 16-channel subtiles per wave (v_mfma_f32_16x16x32)
+    constexpr int TN = BM / WN / 16;          // 16-pixel subtiles per wave
     constexpr int STAGE = (BM + BN) * RB;
     static_assert(AI >= 1 && BI >= 1 && TM >= 1 && TN >= 1, "tile too small for 8-row DMA pieces");
-    static_assert(EPI == 2, "register-only epilogue");
     constexpr int WCH = BN / WM;                          // channels per wave
-    constexpr int EPS = MF == 16 ? TM * TN / 2 : TM * TN * 2;   // epilogue stores per lane
+    constexpr int EPS = TM * TN / 2;                      // epilogue stores per lane
     // the ring; the statistics' cross-wave reduction reuses its first bytes after the last tile
     static_assert(NS * STAGE <= 160 * 1024 && 2 * (BM / (BM / WN)) * BN * 4 <= NS * STAGE, "LDS budget");
     __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
@@ -459,81 +408,53 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
         a_off[j] = ch < a.Nout ? uint32_t(ch) * wrow_b + uint32_t((lane & 7) ^ fsw128(r)) * 16u : OOB;
     }
 
-    // per-lane fragment read offsets inside a stage (subtile i / j adds MF * RB * i: fsw128 is 16-periodic).
-    // 16x16x32: lane (fc, fr) reads row fr of the subtile, 16-B chunk kk * 4 + fc of the 128-B row; 32x32x16: lane
-    // (h, p) reads row p, chunk kk * 4 + 2 s + h for K slice s (the operand layout of cdna_hip_programming.md §3)
-    uint32_t offA[2 * KS], offB[2 * KS];
+    // per-lane fragment read offsets inside a stage (subtile i / j adds 16 * RB * i: fsw128 is 16-periodic): lane
+    // (fc, fr) reads row fr of the subtile, 16-B chunk kk * 4 + fc of the 128-B row
+    uint32_t offA[2], offB[2];
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int lr = MF == 16 ? fr : (lane & 31);
-            const int ch = MF == 16 ? kk * 4 + fc : kk * 4 + 2 * s + (lane >> 5);
-            const int ra = wr * (BN / WM) + lr, rb = wc * (BM / WN) + lr;
-            offA[kk * KS + s] = uint32_t(ra * RB + ((ch ^ fsw128(ra)) << 4));
-            offB[kk * KS + s] = uint32_t(BN * RB + rb * RB + ((ch ^ fsw128(rb)) << 4));
-        }
-    bf16x8 f0a[TM * KS], f0b[TN * KS], f1a[TM * KS], f1b[TN * KS];
+    for (int kk = 0; kk < 2; ++kk) {
+        const int ch = kk * 4 + fc;
+        const int ra = wr * (BN / WM) + fr, rb = wc * (BM / WN) + fr;
+        offA[kk] = uint32_t(ra * RB + ((ch ^ fsw128(ra)) << 4));
+        offB[kk] = uint32_t(BN * RB + rb * RB + ((ch ^ fsw128(rb)) << 4));
+    }
+    bf16x8 f0a[TM], f0b[TN], f1a[TM], f1b[TN];
     auto read_frags = [&](bf16x8* fa, bf16x8* fb, int slot_off, int kk) {     // slot_off: the ring slot's byte offset
+        const char* As = smem + slot_off + offA[kk];
+        const char* Bs = smem + slot_off + offB[kk];
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const char* As = smem + slot_off + offA[kk * KS + s];
-            const char* Bs = smem + slot_off + offB[kk * KS + s];
+        for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * RB);
 #pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i * KS + s] = *reinterpret_cast<const bf16x8*>(As + i * MF * RB);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j * KS + s] = *reinterpret_cast<const bf16x8*>(Bs + j * MF * RB);
-        }
+        for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(Bs + j * 16 * RB);
     };
-    AccT acc[TM][TN];
+    f32x4 acc[TM][TN];
     auto mma = [&](const bf16x8* fa, const bf16x8* fb) {
-        if constexpr ((ABL & 2) != 0) {
 #pragma unroll
-            for (int i = 0; i < TM * KS; ++i) asm volatile("" ::"v"(fa[i]));
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN * KS; ++j) asm volatile("" ::"v"(fb[j]));
-            return;
-        }
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const bf16x8 av = fa[i * KS + s], bv = fb[j * KS + s];
-                    if constexpr (MF == 16) {
-                        if constexpr (MODE == PF)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av),
-                                                                                __builtin_bit_cast(f16x8, bv), acc[i][j],
-                                                                                0, 0, 0);
-                        else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[i][j], 0, 0, 0);
-                    } else {
-                        if constexpr (MODE == PF)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av),
-                                                                                __builtin_bit_cast(f16x8, bv), acc[i][j],
-                                                                                0, 0, 0);
-                        else
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[i][j], 0, 0, 0);
-                    }
-                }
+            for (int j = 0; j < TN; ++j) {
+                if constexpr (MODE == PF)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, fa[i]),
+                                                                        __builtin_bit_cast(f16x8, fb[j]), acc[i][j], 0,
+                                                                        0, 0);
+                else
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+            }
     };
     auto zero_acc = [&]() {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < NR; ++r) acc[i][j][r] = 0.f;
+            for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     };
 
-    float ssum[TM][NR], ssq[TM][NR];
+    float ssum[TM][4], ssq[TM][4];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int r = 0; r < NR; ++r) ssum[i][r] = ssq[i][r] = 0.f;
+        for (int r = 0; r < 4; ++r) ssum[i][r] = ssq[i][r] = 0.f;
 
-    Issuer<BM, BN, NW, MODE, ABL, C1, TO> is(a, wave, lane, mt_lo, qstride, ntile);
+    Issuer<BM, BN, NW, MODE, C1, TO> is(a, wave, lane, mt_lo, qstride, ntile);
     is.start();
 
     // prologue: stages 0..2 in flight (stages past the stream's end fetch nothing); stage 0 landed
@@ -546,7 +467,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
     vm_wait<(NS - 1) * DPS>();
     step_barrier();
     if (total > 0) read_frags(f0a, f0b, 0, 0);
-    int boff = 0;                             // LP 2: the computing slot's byte offset (buf * STAGE)
+    int boff = 0;                             // NESTED: the computing slot's byte offset (buf * STAGE)
 
     // compute side: one K step per iteration; tiles end inside the stream
     int ct = 0, ck = 0, cnk = C1 ? a.KH * a.KW * kc : 0, buf = 0;
@@ -567,14 +488,10 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
     // into the freed slot between the second half's MFMAs; the next stage's first-half reads.  keep_epi: a tile's
     // first step after an epilogue, whose stores may stay in flight across the wait; live: stage g+NS is in the stream
     auto kstep = [&](bool keep_epi, bool live) __attribute__((always_inline)) {
-        const int cur = LP == 2 ? boff : buf * STAGE;
+        const int cur = NESTED ? boff : buf * STAGE;
         read_frags(f1a, f1b, cur, 1);
         mma(f0a, f0b);
-        constexpr int MH = TM * TN * KS;                                            // MFMAs per half
-        if constexpr (RO == 1) {
-            __builtin_amdgcn_sched_group_barrier(0x100, (TM + TN) * KS, 0);        // this step's second-half reads
-            __builtin_amdgcn_sched_group_barrier(0x008, MH, 0);                     // first-half MFMAs
-        }
+        constexpr int MH = TM * TN;                                                 // MFMAs per half
         // stage g+1 must have landed (own DMAs); stage g+2 may stay in flight (every step issues DPS DMAs,
         // live or not, so the count is constant); in a tile's first step the previous tile's epilogue stores,
         // issued after stage g+2's pieces, may stay in flight too
@@ -587,27 +504,17 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
         const int nbuf = buf == NS - 1 ? 0 : buf + 1;
         const int nboff = boff == (NS - 1) * STAGE ? 0 : boff + STAGE;
         is.issue_dma(smem + cur, wres, a_off, live);
-        read_frags(f0a, f0b, LP == 2 ? nboff : nbuf * STAGE, 0);
+        read_frags(f0a, f0b, NESTED ? nboff : nbuf * STAGE, 0);
         mma(f1a, f1b);
-        if constexpr (RO == 1) {
-            __builtin_amdgcn_sched_group_barrier(0x100, (TM + TN) * KS, 0);        // next-stage reads first
 #pragma unroll
-            for (int d = 0; d < DPS; ++d) {
-                __builtin_amdgcn_sched_group_barrier(0x008, MH / (DPS + 1), 0);     // MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                 // one DMA
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, MH - DPS * (MH / (DPS + 1)), 0);
-        } else {
-#pragma unroll
-            for (int d = 0; d < DPS; ++d) {
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                 // one DMA
-                __builtin_amdgcn_sched_group_barrier(0x008, MH / (DPS + 1), 0);     // MFMAs
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, (TM + TN) * KS, 0);        // next-stage reads
-            __builtin_amdgcn_sched_group_barrier(0x008, MH - DPS * (MH / (DPS + 1)), 0);
+        for (int d = 0; d < DPS; ++d) {
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                     // one DMA
+            __builtin_amdgcn_sched_group_barrier(0x008, MH / (DPS + 1), 0);         // MFMAs
         }
+        __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);                   // next-stage reads
+        __builtin_amdgcn_sched_group_barrier(0x008, MH - DPS * (MH / (DPS + 1)), 0);
         is.advance();
-        if constexpr (LP == 2) boff = nboff;
+        if constexpr (NESTED) boff = nboff;
         else buf = nbuf;
     };
     // the tile's epilogue
@@ -651,23 +558,15 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
                     if (pix >= is.ohw) { pix -= is.ohw; ++n; }
                     return uint32_t((int64_t(n) * e.r_bs + int64_t(pix) * e.r_ld + wch0) * 2);
                 };
-                if constexpr (MF == 16)
-                    epilogue_regs_x<TM, TN>(acc, ssum, ssq, false, lane, wch0, a.Nout, yres, true, false, pix_off, pix_ok,
-                                            &ee, res_off);
-                else
-                    epilogue_regs32_x<TM, TN>(acc, ssum, ssq, false, lane, wch0, a.Nout, yres, true, false, pix_off,
-                                              pix_ok, &ee, res_off);
+                epilogue_regs_x<TM, TN>(acc, ssum, ssq, false, lane, wch0, a.Nout, yres, true, false, pix_off, pix_ok,
+                                        &ee, res_off);
             } else {
-                if constexpr (MF == 16)
-                    epilogue_regs<TM, TN>(acc, ssum, ssq, a.st_sum != nullptr, lane, wch0, a.Nout, yres,
-                                          a.out_f32 == 2, a.accumulate != 0, pix_off, pix_ok);
-                else
-                    epilogue_regs32_x<TM, TN>(acc, ssum, ssq, a.st_sum != nullptr, lane, wch0, a.Nout, yres,
-                                              a.out_f32 == 2, a.accumulate != 0, pix_off, pix_ok, nullptr, pix_off);
+                epilogue_regs<TM, TN>(acc, ssum, ssq, a.st_sum != nullptr, lane, wch0, a.Nout, yres, a.out_f32 == 2,
+                                      a.accumulate != 0, pix_off, pix_ok);
             }
         }
     };
-    if constexpr (LP >= 1) {
+    if constexpr (NESTED) {
         int g = 0;
         for (int t = 0; t < ntile; ++t) {
             if (t > 0) {
@@ -677,15 +576,11 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
                 if (c_tp >= is.ohw) { c_tp -= is.ohw; ++c_tn; }
             }
             zero_acc();
-            kstep(EPI == 2 && t > 0, g + NS < total);
+            kstep(t > 0, g + NS < total);
             ++g;
-            if constexpr (LP == 2) {
-                // the stream's last NS stages fetch nothing: live while g < glim
-                const int glim = total - NS;
-                for (int k = 1; k < cnk; ++k, ++g) kstep(false, g < glim);
-            } else {
-                for (int k = 1; k < cnk; ++k, ++g) kstep(false, g + NS < total);
-            }
+            // the stream's last NS stages fetch nothing: live while g < glim
+            const int glim = total - NS;
+            for (int k = 1; k < cnk; ++k, ++g) kstep(false, g < glim);
             epilogue();
         }
     } else {
@@ -709,7 +604,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
                 cnk = cc.ntap * kc;
                 zero_acc();
             }
-            kstep(EPI == 2 && ck == 0 && ct > 0, g + NS < total);
+            kstep(ck == 0 && ct > 0, g + NS < total);
             if (++ck < cnk) continue;
             ck = 0;
             ++ct;
@@ -726,17 +621,16 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
+            for (int r = 0; r < 4; ++r) {
                 float s = ssum[i][r], sq = ssq[i][r];
-                // over the lanes holding other pixels of the same channel: 16 (16x16 layout) or 32 (32x32)
+                // over the 16 lanes holding other pixels of the same channel
 #pragma unroll
-                for (int o = 1; o < MF; o <<= 1) {
+                for (int o = 1; o < 16; o <<= 1) {
                     s += __shfl_xor(s, o, 64);
                     sq += __shfl_xor(sq, o, 64);
                 }
-                if ((lane & (MF - 1)) == 0) {
-                    const int cl = MF == 16 ? wr * (BN / WM) + i * 16 + fc * 4 + r
-                                            : wr * (BN / WM) + i * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+                if (fr == 0) {
+                    const int cl = wr * (BN / WM) + i * 16 + fc * 4 + r;
                     red[0][wc][cl] = s;
                     red[1][wc][cl] = sq;
                 }
@@ -757,29 +651,18 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) conv_pipe_kernel(PipeArgs a, 
     }
 }
 
-// tile configurations: 0 / 1 the shipped 16-wave 256 x 128 and 8-wave 256 x 64 tiles; 2 experimental
-// (ym_pipe_set_exp 1): 256 x 128 on 8 waves of 64 x 64 — round 5, same process: within +-3.5 % of the 16-wave tile
-// on every layer with 31 % fewer LDS-array cycles (profiles/r05/pipe_wave_tile_ab.txt), so the LDS array does not
-// bound it.  (256 x 256 / 512 x 128 tiles on 8 waves of 128 x 64 need 128 accumulator registers per lane and
+// tile configurations (PipePlan::cfg): 0 the 256 x 128 tile, 1 the 256 x 64 tile.  Training runs 256 x 128 on 16 waves
+// of 32 x 64 (four per SIMD, 127 VGPRs): same staging and LDS as 8 waves of 64 x 64, 1.5x the fragment reads, but while
+// some waves of a SIMD issue their DMA pieces or wait at the barrier others issue MFMAs — same-process A/B against
+// 8 waves: fwd / dgrad 0-7 % faster on every layer measured (1x1 80x80 192->256 -6.8 / -6.2 %, 3x3 40x40 128->128
+// -3.3 / -6.7 %, stride-2 80x80 equal).  The 8-wave 256 x 128 tile remains only as the eval instance of cfg 0: the
+// 16-wave tile's 127 VGPRs leave no room for the eval epilogue at four waves per SIMD.  256 x 64 runs on 8 waves of
+// 64 x 32 everywhere.  (256 x 256 / 512 x 128 tiles on 8 waves of 128 x 64 need 128 accumulator registers per lane and
 // spilled 213-439 VGPRs at the 256-register cap of two waves per SIMD: not kept.)
 struct Cfg {
     int bm, bn;
 };
-constexpr Cfg kCfg[] = {{256, 128}, {256, 64}, {256, 128}};
-
-// 256 x 128 tiles run on 16 waves of 32 x 64 (four per SIMD, 127 VGPRs): same staging and LDS as 8 waves
-// of 64 x 64, 1.5x the fragment reads, but while some waves of a SIMD issue their DMA pieces or wait at
-// the barrier others issue MFMAs — same-process A/B against 8 waves: fwd / dgrad 0-7 % faster on every
-// layer measured (1x1 80x80 192->256 -6.8 / -6.2 %, 3x3 40x40 128->128 -3.3 / -6.7 %, stride-2 80x80 equal)
-// cfg 0 / 1 / 2 tiles (kCfg) of one control path (C1), MFMA shape (MF) and issue order (RO)
-template <int MODE, bool C1, int MF, int RO, int LP = 0, int TO = 0>
-void launch_tiles(int cfg, const PipeArgs& a, int grid, hipStream_t st) {
-    switch (cfg) {
-        case 0: conv_pipe_kernel<256, 128, 4, 4, MODE, 2, 3, 0, C1, false, MF, RO, LP, TO><<<dim3(grid), dim3(1024), 0, st>>>(a, EvalArgs{}); break;
-        case 1: conv_pipe_kernel<256, 64, 1, 8, MODE, 2, 3, 0, C1, false, MF, RO, LP, TO><<<dim3(grid), dim3(512), 0, st>>>(a, EvalArgs{}); break;
-        default: conv_pipe_kernel<256, 128, 2, 4, MODE, 2, 3, 0, C1, false, MF, RO, LP, TO><<<dim3(grid), dim3(512), 0, st>>>(a, EvalArgs{}); break;
-    }
-}
+constexpr Cfg kCfg[] = {{256, 128}, {256, 64}};
 
 // the tap-innermost K order (Issuer TO 1) where it measured faster: stride-2 3x3 forwards reading maps >= 128 wide (op 6,
 // 128 -> 128 at 160x160 -> 80x80: -12 % time, -27 % HBM fetch; profiles/r06/pipe_taporder_ab.txt) — there one tile's
@@ -787,80 +670,32 @@ void launch_tiles(int cfg, const PipeArgs& a, int grid, hipStream_t st) {
 // 0..+5 % slower (a tap_setup per K step, and the footprint fits L2 either way)
 inline bool tap_inner(const PipeArgs& a) { return a.stride == 2 && a.KH == 3 && a.GW >= 128; }
 
-template <int MODE>
-void launch_mode(int cfg, const PipeArgs& a, int grid, hipStream_t st) {
-    const bool c1 = a.ncls == 1 && int64_t(a.OH) * a.OW >= kCfg[cfg].bm && g_pipe_exp != 20;
-#ifdef YM_EXPERIMENTS
-    if (cfg == 0 && g_pipe_exp >= 10 && g_pipe_exp < 20) {
-        switch (g_pipe_exp) {
-            case 10: conv_pipe_kernel<256, 128, 4, 4, MODE, 2, 3, 1, true><<<dim3(grid), dim3(1024), 0, st>>>(a, EvalArgs{}); return;
-            case 11: conv_pipe_kernel<256, 128, 4, 4, MODE, 2, 3, 2, true><<<dim3(grid), dim3(1024), 0, st>>>(a, EvalArgs{}); return;
-            case 12: conv_pipe_kernel<256, 128, 4, 4, MODE, 2, 3, 4, true><<<dim3(grid), dim3(1024), 0, st>>>(a, EvalArgs{}); return;
-            default: conv_pipe_kernel<256, 128, 4, 4, MODE, 2, 3, 8, true><<<dim3(grid), dim3(1024), 0, st>>>(a, EvalArgs{}); return;
+// the instances the library ships, all of them: per training tile the forward and the data gradient on the generic
+// (class-search, flat loop) and the single-class (C1, nested loop) control paths, the C1 forward also tap-innermost;
+// per tile one eval instance (C1 forward, flat loop)
+enum Inst { FWD_GEN, FWD_C1, FWD_C1_TAP, DGRAD_GEN, DGRAD_C1, EVAL };
+
+void launch(int cfg, Inst inst, const PipeArgs& a, const EvalArgs& e, int grid, hipStream_t st) {
+    const dim3 g(grid), w16(1024), w8(512);
+    if (cfg == 0) {
+        switch (inst) {  //                 BM   BN  WM WN MODE  C1     EV     NESTED TO
+            case FWD_GEN:    conv_pipe_kernel<256, 128, 4, 4, PF, false, false, false, 0><<<g, w16, 0, st>>>(a, e); break;
+            case FWD_C1:     conv_pipe_kernel<256, 128, 4, 4, PF, true,  false, true,  0><<<g, w16, 0, st>>>(a, e); break;
+            case FWD_C1_TAP: conv_pipe_kernel<256, 128, 4, 4, PF, true,  false, true,  1><<<g, w16, 0, st>>>(a, e); break;
+            case DGRAD_GEN:  conv_pipe_kernel<256, 128, 4, 4, PD, false, false, false, 0><<<g, w16, 0, st>>>(a, e); break;
+            case DGRAD_C1:   conv_pipe_kernel<256, 128, 4, 4, PD, true,  false, true,  0><<<g, w16, 0, st>>>(a, e); break;
+            case EVAL:       conv_pipe_kernel<256, 128, 2, 4, PF, true,  true,  false, 0><<<g, w8, 0, st>>>(a, e); break;
         }
-    }
-#endif
-#ifdef YM_EXPERIMENTS
-    const int mf = g_pipe_mfma, ro = g_pipe_order;
-    const int c = mf == 2 && cfg == 0 ? 2 : cfg;
-    if (c1) {
-        if (mf != 0) {
-            if (ro) launch_tiles<MODE, true, 32, 1>(c, a, grid, st);
-            else launch_tiles<MODE, true, 32, 0>(c, a, grid, st);
-        } else {
-            if (ro) launch_tiles<MODE, true, 16, 1>(c, a, grid, st);
-            else if (MODE == PF && (g_pipe_taporder == 1 || (g_pipe_taporder < 0 && tap_inner(a)))) {
-                if constexpr (MODE == PF) launch_tiles<MODE, true, 16, 0, 2, 1>(c, a, grid, st);
-            }
-            else if (g_pipe_loop == 0) launch_tiles<MODE, true, 16, 0, 0>(c, a, grid, st);
-            else if (g_pipe_loop == 1) launch_tiles<MODE, true, 16, 0, 1>(c, a, grid, st);
-            else launch_tiles<MODE, true, 16, 0, 2>(c, a, grid, st);
-        }
-        return;
-    }
-    if (mf != 0) launch_tiles<MODE, false, 32, 0>(c, a, grid, st);
-    else launch_tiles<MODE, false, 16, 0>(c, a, grid, st);
-#else
-    if (c1) {
-        if constexpr (MODE == PF) {
-            if (tap_inner(a)) {
-                launch_tiles<MODE, true, 16, 0, 2, 1>(cfg, a, grid, st);
-                return;
-            }
-        }
-        launch_tiles<MODE, true, 16, 0, 2>(cfg, a, grid, st);
     } else {
-        launch_tiles<MODE, false, 16, 0>(cfg, a, grid, st);
+        switch (inst) {
+            case FWD_GEN:    conv_pipe_kernel<256, 64, 1, 8, PF, false, false, false, 0><<<g, w8, 0, st>>>(a, e); break;
+            case FWD_C1:     conv_pipe_kernel<256, 64, 1, 8, PF, true,  false, true,  0><<<g, w8, 0, st>>>(a, e); break;
+            case FWD_C1_TAP: conv_pipe_kernel<256, 64, 1, 8, PF, true,  false, true,  1><<<g, w8, 0, st>>>(a, e); break;
+            case DGRAD_GEN:  conv_pipe_kernel<256, 64, 1, 8, PD, false, false, false, 0><<<g, w8, 0, st>>>(a, e); break;
+            case DGRAD_C1:   conv_pipe_kernel<256, 64, 1, 8, PD, true,  false, true,  0><<<g, w8, 0, st>>>(a, e); break;
+            case EVAL:       conv_pipe_kernel<256, 64, 1, 8, PF, true,  true,  false, 0><<<g, w8, 0, st>>>(a, e); break;
+        }
     }
-#endif
-}
-
-// the eval instance (EV): cfg 1 / 2 tiles on 8 waves (the 16-wave 256 x 128 tile's 127 VGPRs leave no room for the
-// eval epilogue at four waves per SIMD; cfg 0 runs as the 8-wave cfg 2)
-void launch_eval(int cfg, const PipeArgs& a, const EvalArgs& e, int grid, hipStream_t st) {
-#ifdef YM_EXPERIMENTS
-    if (g_pipe_mfma != 0) {
-        if (cfg == 1) conv_pipe_kernel<256, 64, 1, 8, PF, 2, 3, 0, true, true, 32><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-        else conv_pipe_kernel<256, 128, 2, 4, PF, 2, 3, 0, true, true, 32><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-        return;
-    }
-    if (g_pipe_eval_loop == 2) {
-        // the nested loop form of the training instances: inference bs 1 / 8 / 128 within the run-to-run spread of the
-        // flat form (profiles/r06/pipe_eval_loop_ab.txt), so the eval instance keeps the flat loop
-        if (cfg == 1) conv_pipe_kernel<256, 64, 1, 8, PF, 2, 3, 0, true, true, 16, 0, 2><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-        else conv_pipe_kernel<256, 128, 2, 4, PF, 2, 3, 0, true, true, 16, 0, 2><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-        return;
-    }
-#endif
-    if (cfg == 1) conv_pipe_kernel<256, 64, 1, 8, PF, 2, 3, 0, true, true><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-    else conv_pipe_kernel<256, 128, 2, 4, PF, 2, 3, 0, true, true><<<dim3(grid), dim3(512), 0, st>>>(a, e);
-}
-
-void launch_cfg(int mode, int cfg, const PipeArgs& a, int grid, hipStream_t st) {
-    // both directions: the register-only epilogue (round 4 for the forward, with the statistics masked by a compare:
-    // same-process A/B 2-7 % faster on every pipelined forward, profiles/r04/pipe_fwd_reg_epilogue_ab.txt)
-    if (mode == PF) launch_mode<PF>(cfg, a, grid, st);
-    else launch_mode<PD>(cfg, a, grid, st);
 }
 
 }  // namespace
@@ -887,7 +722,6 @@ PipePlan pipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol) {
     if (int64_t(OH) * OW >= (int64_t(1) << 24) || OH >= (1 << 16)) return p;
     const int64_t M = pol.select_n(d) * ((OH + os - 1) / os) * ((OW + os - 1) / os) * os * os;
     p.cfg = nout >= 128 ? 0 : 1;
-    if (g_pipe_exp == 1 && nout >= 128) p.cfg = 2;
     const int bm = kCfg[p.cfg].bm, bn = kCfg[p.cfg].bn;
     const int ntiles = (nout + bn - 1) / bn;
     const int64_t tiles = (M / bm) * ntiles;
@@ -904,41 +738,6 @@ PipePlan pipe_plan(const ym_conv_desc* d, int dgrad, const ConvPolicy& pol) {
     p.ok = 1;
     return p;
 }
-
-#ifdef YM_EXPERIMENTS
-int pipe_order_exp() { return g_pipe_order; }
-
-extern "C" int ym_conv_set_pipe_order(int mode) {
-    // K-step issue order of the pipelined kernel (conv_pipe_kernel RO: 0 default, 1 fragment reads pinned first)
-    return g_pipe_order.set(mode < 0 || mode > 1 ? 0 : mode);
-}
-
-extern "C" int ym_conv_set_pipe_loop(int mode) {
-    // loop form of the pipelined kernel's single-class path (conv_pipe_kernel LP: 0 flat, 1 nested tiles x K steps,
-    // 2 nested with the slot offset carried)
-    return g_pipe_loop.set(mode < 0 || mode > 2 ? 2 : mode);
-}
-
-extern "C" int ym_conv_set_pipe_eval_loop(int mode) {
-    // loop form of the pipelined kernel's eval instance (conv_pipe_kernel LP: 0 flat, 2 nested); returns the previous
-    return g_pipe_eval_loop.set(mode == 2 ? 2 : 0);
-}
-
-extern "C" int ym_conv_set_pipe_taporder(int mode) {
-    // K order of the pipelined kernel's single-class forward (conv_pipe_kernel TO): 0 chunk innermost, 1 tap innermost,
-    // anything else the shipped rule (tap_inner)
-    return g_pipe_taporder.set(mode < 0 || mode > 1 ? -1 : mode);
-}
-
-extern "C" int ym_conv_set_pipe_mfma(int mode) {
-    // MFMA shape of the pipelined implicit GEMM (see g_pipe_mfma); out of range restores the default 0
-    return g_pipe_mfma.set(mode < 0 || mode > 2 ? 0 : mode);
-}
-
-extern "C" int ym_pipe_set_exp(int v) {
-    return g_pipe_exp.set(v);
-}
-#endif
 
 // operands, views and map geometry of d's forward (dgrad 0) or data gradient
 static void pipe_geometry(PipeArgs& a, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y) {
@@ -971,13 +770,16 @@ int pipe_launch(const PipePlan& p, const ym_conv_desc* d, int dgrad, const uint1
     }
     a.mt_pre[a.ncls] = acc;
     if (!dgrad && st_sum) a.fold = bn_fold_args(fold);
-    launch_cfg(dgrad ? PD : PF, p.cfg, a, p.grid, st);
+    // the single-class path: one output class on maps of >= BM pixels
+    const bool c1 = a.ncls == 1 && int64_t(a.OH) * a.OW >= bm;
+    const Inst inst = dgrad ? (c1 ? DGRAD_C1 : DGRAD_GEN) : !c1 ? FWD_GEN : tap_inner(a) ? FWD_C1_TAP : FWD_C1;
+    launch(p.cfg, inst, a, EvalArgs{}, p.grid, st);
     return YM_OK;
 }
 
 bool pipe_eval_ok(const PipePlan& p, const ym_conv_desc* d) {
     // the eval instance is the single-class (C1) forward: maps of >= BM pixels, the shipped control path
-    return p.ok && int64_t(d->oh) * d->ow >= kCfg[p.cfg].bm && g_pipe_exp != 20 && d->out_f32 == 2 && !d->accumulate;
+    return p.ok && int64_t(d->oh) * d->ow >= kCfg[p.cfg].bm && d->out_f32 == 2 && !d->accumulate;
 }
 
 int pipe_launch_eval(const PipePlan& p, const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, uint16_t* y,
@@ -986,14 +788,12 @@ int pipe_launch_eval(const PipePlan& p, const ym_conv_desc* d, const uint16_t* x
     PipeArgs a{};
     pipe_geometry(a, d, 0, x, w, y);
     a.out_f32 = 2;
-    // cfg 0 runs as the 8-wave 256 x 128 instance (same tile, grid and rows)
-    const int cfg = p.cfg == 1 ? 1 : 2;
-    const int bm = kCfg[cfg].bm, bn = kCfg[cfg].bn;
+    const int bm = kCfg[p.cfg].bm, bn = kCfg[p.cfg].bn;
     a.ntiles = (a.Nout + bn - 1) / bn;
     a.ncls = 1;
     a.mt_pre[0] = 0;
     a.mt_pre[1] = int((int64_t(a.N) * a.OH * a.OW + bm - 1) / bm);
-    launch_eval(cfg, a, e, p.grid, st);
+    launch(p.cfg, EVAL, a, e, p.grid, st);
     return 0;
 }
 

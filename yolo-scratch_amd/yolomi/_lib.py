@@ -73,8 +73,9 @@ class AugColour(ctypes.Structure):
 
 
 R = _c.c_int
-# name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (its YM_EXPERIMENTS block
-# excepted: the measurement library's)
+# name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (the setters of the kernel
+# variants measured and rejected in rounds 5 / 6 went with their code: DESIGN §12 / §13, profiles/r05, profiles/r06; the code
+# is in history at the parent of the commit that removed them)
 SIGNATURES = {
     "ym_last_error": (_c.c_char_p, []),
     "ym_version": (R, []),
