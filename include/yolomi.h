@@ -442,6 +442,25 @@ int ym_tal_assign(const float* pd_scores, const float* pd_bboxes, const float* a
                   const float* gt_bboxes, const float* mask_gt, int64_t B, int64_t A, int nc, int M, float alpha,
                   float beta, float eps, void* workspace, size_t workspace_bytes, float* target_labels, float* target_bboxes, float* target_scores,
                   uint8_t* fg_mask, int64_t* target_gt_idx, void* stream);
+/* The top-k task-aligned assigner, beside the in-box one above and off by default.
+ * Per valid GT: its `topk` in-box anchors of largest metric = score^alpha * IoU^beta (ties: lowest
+ * anchor; fewer in-box anchors: all of them; none: no positives, nothing is forced).  Per anchor: the
+ * claiming GT of largest IoU (ties: lowest GT), else background.  norm = metric * maxo(g) / (maxm(g) + eps),
+ * the maxima over the anchors finally assigned to g.  1 <= topk <= 64.
+ * ym_loss_fwd_topk is ym_loss_fwd with this assigner (alpha 0.5, beta 4, eps 1e-9): same arguments plus
+ * `topk`, same out[0..5]; its workspace begins with ym_loss_fwd's layout, so ym_loss_bwd and
+ * ym_loss_assignment take it as they are.  ym_tal_assign_topk is ym_tal_assign with this assigner. */
+size_t ym_loss_topk_workspace_size(int64_t B, int64_t A, int M, int topk);
+int ym_loss_fwd_topk(const float* head, int64_t B, int64_t A, int nc, int nl, const int* level_h, const int* level_w,
+                     const float* strides, const int64_t* batch_idx, const int64_t* cls, const float* bboxes,
+                     int64_t n_targets, int M, float imgsz_h, float imgsz_w, void* workspace, size_t workspace_bytes,
+                     float* gt_box, float* gt_lab, int* gt_valid, float* out, int topk, void* stream);
+size_t ym_tal_assign_topk_workspace_size(int64_t B, int64_t A, int M, int topk);
+int ym_tal_assign_topk(const float* pd_scores, const float* pd_bboxes, const float* anc_points,
+                       const float* gt_labels, const float* gt_bboxes, const float* mask_gt, int64_t B, int64_t A,
+                       int nc, int M, float alpha, float beta, float eps, void* workspace, size_t workspace_bytes,
+                       float* target_labels, float* target_bboxes, float* target_scores, uint8_t* fg_mask,
+                       int64_t* target_gt_idx, int topk, void* stream);
 /* BboxLoss.forward (losses/yolo_v8_loss.py:280-324): pred_dist (B,A,64), pred_bboxes / target_bboxes
  * (B,A,4) grid units, anchor_points (A,2), target_scores (B,A,nc), tss device scalar (target_scores_sum),
  * fg_mask (B,A) uint8.  out[0] = loss_iou, out[1] = loss_dfl.  The backward writes

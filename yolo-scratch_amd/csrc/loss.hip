@@ -20,6 +20,9 @@
 // select_highest_overlaps, the sequential loop 2 on compact per-GT state, final
 // select, target-score norm) -> loss_partial (per anchor BCE / CIoU / DFL) ->
 // loss_final.  ym_loss_bwd recomputes per anchor and writes d loss / d head.
+// ym_loss_fwd_topk puts the standard top-k task-aligned assignment (no reference counterpart; off by default) in
+// front of the same loss_partial / loss_final: gt_prep -> topk_decode -> topk_select (one workgroup per (gt, image))
+// -> topk_resolve -> topk_norm, leaving tgi / fg / norm where ym_loss_bwd reads them.
 #include <algorithm>
 
 #include "common.h"
@@ -156,6 +159,11 @@ struct HeadSrc {
         return make_float4(pb.x * s, pb.y * s, pb.z * s, pb.w * s);
     }
     __device__ float score(int b, int64_t a, int lab) const { return sigm(head[(int64_t(b) * A + a) * no + 64 + lab]); }
+    __device__ void centre(int64_t a, float& cx, float& cy) const {
+        float ax, ay, s;
+        anchor_of(L, a, ax, ay, s);
+        cx = ax * s; cy = ay * s;
+    }
 };
 
 struct PlainSrc {
@@ -175,6 +183,7 @@ struct PlainSrc {
         return make_float4(r[0], r[1], r[2], r[3]);
     }
     __device__ float score(int b, int64_t a, int lab) const { return scores[(int64_t(b) * A + a) * nc + lab]; }
+    __device__ void centre(int64_t a, float& cx, float& cy) const { cx = anc[2 * a]; cy = anc[2 * a + 1]; }
 };
 
 // ---------------------------------------------------------------- assignment, pass 1
@@ -757,6 +766,151 @@ __global__ void __launch_bounds__(256) bbox_loss_bwd_kernel(BoxIn in, const floa
     }
 }
 
+// ---------------------------------------------------------------- top-k task-aligned assignment
+// The standard rule beside the in-box one above: a GT's candidates are its `k` in-box anchors of largest
+// metric = score^alpha * IoU^beta (ties: lowest anchor), an anchor claimed by several GTs goes to the claimant
+// of largest IoU (ties: lowest gt), norm = metric * maxo(g) / (maxm(g) + eps) with the maxima over the anchors
+// finally assigned to g.  No forced assignment.  Integer atomics only (max over packed keys: the result does
+// not depend on the order of arrival), so runs are bit-identical.
+constexpr int TOPK_MAX = 64;         // largest k
+constexpr int TOPK_CHUNK = 1024;     // anchors whose keys are cached in LDS at a time
+constexpr int TOPK_THREADS = 256;
+
+struct TopkWs {
+    unsigned long long* claim;   // [B][A] packed (iou bits << 32 | ~g) of the winning claimant; 0: background (zeroed)
+    unsigned* maxm;              // [B][M] bits of the largest metric over the anchors assigned to g     (zeroed)
+    unsigned* maxo;              // [B][M] bits of the largest IoU over them                             (zeroed)
+};
+
+// an exponent of exactly 1 is the value, 0.5 the square root (as assign_norm_kernel's alpha), else powf
+__device__ __forceinline__ float tal_pow(float v, float e) {
+    return e == 1.0f ? v : (e == 0.5f ? sqrtf(v) : powf(v, e));
+}
+
+template <class Src>
+__device__ __forceinline__ float tal_iou(const Src& src, const AssignWs& w, int b, int64_t a, const float4& gb) {
+    const float4 pb = src.pixbox(b, a, w);
+    const float iou = iou_xyxy(pb.x, pb.y, pb.z, pb.w, gb.x, gb.y, gb.z, gb.w);
+    return iou < 0.f ? 0.f : iou;
+}
+
+// the fused loss's decode pass: pbox for every anchor (assign_scan_kernel does this on the in-box path)
+__global__ void __launch_bounds__(256) topk_decode_kernel(HeadSrc src, int64_t A, AssignWs w) {
+    const int b = blockIdx.y;
+    const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (a >= A) return;
+    float px1, py1, px2, py2, cx, cy;
+    src.box(b, a, w, px1, py1, px2, py2, cx, cy);
+}
+
+// One workgroup per (gt, image).  The image's anchors are walked TOPK_CHUNK at a time: every in-box anchor's key
+// (metric bits << 32 | ~anchor: one integer compare orders by metric descending, then anchor ascending; an in-box
+// key is never 0) goes to the LDS cache behind the k best keys of the chunks before, and k rounds of a
+// workgroup-wide "largest key below the last one" leave the k best of both.  Chunks without an in-box anchor (most
+// of them, for a small box) skip the rounds.  The k survivors then claim their anchors.
+template <class Src>
+__global__ void __launch_bounds__(TOPK_THREADS) topk_select_kernel(Src src, int64_t A, int nc,
+                                                                   const float4* __restrict__ gt_box,
+                                                                   const float* __restrict__ gt_lab,
+                                                                   const int* __restrict__ gt_valid, int M, int k,
+                                                                   float alpha, float beta, AssignWs w, TopkWs t) {
+    __shared__ unsigned long long cache[TOPK_MAX + TOPK_CHUNK];   // [0, TOPK_MAX): best so far, then the chunk
+    __shared__ unsigned long long ntop[TOPK_MAX];
+    __shared__ unsigned long long s_w[2][TOPK_THREADS / 64];
+    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!gt_valid[b * M + g]) return;                             // workgroup-uniform
+    const float4 gb = gt_box[b * M + g];
+    const int lab = min(max(int(gt_lab[b * M + g]), 0), nc - 1);
+    if (tid < TOPK_MAX) cache[tid] = 0ull;
+    for (int64_t c0 = 0; c0 < A; c0 += TOPK_CHUNK) {
+        int any = 0;
+        for (int i = tid; i < TOPK_CHUNK; i += TOPK_THREADS) {
+            const int64_t a = c0 + i;
+            unsigned long long key = 0ull;
+            if (a < A) {
+                float cx, cy;
+                src.centre(a, cx, cy);
+                const float l = cx - gb.x, tp = cy - gb.y, r = gb.z - cx, bo = gb.w - cy;
+                if (fminf(fminf(l, tp), fminf(r, bo)) > EPS_TAL) {
+                    const float iou = tal_iou(src, w, b, a, gb);
+                    const float metric = tal_pow(src.score(b, a, lab), alpha) * tal_pow(iou, beta);
+                    key = (uint64_t(__float_as_uint(metric)) << 32) | uint64_t(0xffffffffu - uint32_t(a));
+                    any = 1;
+                }
+            }
+            cache[TOPK_MAX + i] = key;
+        }
+        if (!__syncthreads_or(any)) continue;                     // workgroup-uniform
+        unsigned long long prev = ~0ull;
+        int found = 0;
+        for (int r = 0; r < k; ++r) {
+            uint32_t hi = 0u, lo = 0u;
+            for (int i = tid; i < TOPK_MAX + TOPK_CHUNK; i += TOPK_THREADS) {
+                const unsigned long long v = cache[i];
+                if (v < prev && v > ((uint64_t(hi) << 32) | lo)) { hi = uint32_t(v >> 32); lo = uint32_t(v); }
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const uint32_t h2 = __shfl_xor(hi, o, 64), l2 = __shfl_xor(lo, o, 64);
+                if (h2 > hi || (h2 == hi && l2 > lo)) { hi = h2; lo = l2; }
+            }
+            if (lane == 0) s_w[r & 1][wv] = (uint64_t(hi) << 32) | lo;
+            __syncthreads();
+            unsigned long long m = s_w[r & 1][0];
+#pragma unroll
+            for (int q = 1; q < TOPK_THREADS / 64; ++q) m = max(m, s_w[r & 1][q]);
+            if (m == 0ull) break;                                 // fewer than k keys in all: uniform
+            if (tid == 0) ntop[r] = m;
+            prev = m;
+            found = r + 1;
+        }
+        __syncthreads();
+        if (tid < TOPK_MAX) cache[tid] = tid < found ? ntop[tid] : 0ull;
+    }
+    __syncthreads();
+    if (tid < k) {
+        const unsigned long long key = cache[tid];
+        if (key) {
+            const int64_t a = int64_t(0xffffffffu - uint32_t(key));
+            const float iou = tal_iou(src, w, b, a, gb);
+            atomicMax(&t.claim[int64_t(b) * A + a],
+                      (uint64_t(__float_as_uint(iou)) << 32) | uint64_t(0xffffffffu - uint32_t(g)));
+        }
+    }
+}
+
+// per anchor: the winning claimant (largest IoU, then lowest gt) or background; the metric is parked in `norm`
+// and the per-gt maxima over the assigned anchors are taken with integer atomicMax on the (non-negative) float bits
+template <class Src>
+__global__ void __launch_bounds__(256) topk_resolve_kernel(Src src, int64_t A, int nc, const float* __restrict__ gt_lab,
+                                                           int M, float alpha, float beta, AssignWs w, TopkWs t) {
+    const int b = blockIdx.y;
+    const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (a >= A) return;
+    const int64_t i = int64_t(b) * A + a;
+    const unsigned long long c = t.claim[i];
+    if (!c) { w.tgi[i] = 0; w.fg[i] = 0; w.norm[i] = 0.f; return; }
+    const int g = int(0xffffffffu - uint32_t(c));
+    const float iou = __uint_as_float(uint32_t(c >> 32));
+    const int lab = min(max(int(gt_lab[b * M + g]), 0), nc - 1);
+    const float metric = tal_pow(src.score(b, a, lab), alpha) * tal_pow(iou, beta);
+    w.tgi[i] = g;
+    w.fg[i] = 1;
+    w.norm[i] = metric;
+    atomicMax(&t.maxm[b * M + g], __float_as_uint(metric));
+    atomicMax(&t.maxo[b * M + g], __float_as_uint(iou));
+}
+
+__global__ void __launch_bounds__(256) topk_norm_kernel(int64_t A, int M, float eps, AssignWs w, TopkWs t) {
+    const int b = blockIdx.y;
+    const int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (a >= A) return;
+    const int64_t i = int64_t(b) * A + a;
+    if (!w.fg[i]) return;
+    const int g = w.tgi[i];
+    w.norm[i] = w.norm[i] * __uint_as_float(t.maxo[b * M + g]) / (__uint_as_float(t.maxm[b * M + g]) + eps);
+}
+
 inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Carve {
@@ -791,6 +945,37 @@ Carve carve(void* base, int64_t B, int64_t A, int M, int64_t nparts) {
 size_t zero_bytes(int64_t B, int64_t A, int M) {
     size_t BA = size_t(B) * A, BM = size_t(B) * std::max(M, 1);
     return al(BM * 8) + al(BM * 4) + al(BA * 4);
+}
+
+// the top-k region behind the loss carve: one run of zeroed words
+struct TopkCarve {
+    TopkWs t;
+    size_t bytes;
+};
+
+TopkCarve carve_topk(char* p, int64_t B, int64_t A, int M) {
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p ? p + off : nullptr; off += al(n); return r; };
+    TopkCarve c;
+    size_t BA = size_t(B) * A, BM = size_t(B) * std::max(M, 1);
+    c.t.claim = reinterpret_cast<unsigned long long*>(take(BA * 8));
+    c.t.maxm = reinterpret_cast<unsigned*>(take(BM * 4));
+    c.t.maxo = reinterpret_cast<unsigned*>(take(BM * 4));
+    c.bytes = off;
+    return c;
+}
+
+// select -> resolve -> norm on a source whose boxes are readable through pixbox (HeadSrc: after topk_decode_kernel)
+template <class Src>
+int topk_assign(const Src& src, int64_t B, int64_t A, int nc, const float4* gb, const float* gl, const int* valid, int M,
+                int k, float alpha, float beta, float eps, const AssignWs& w, const TopkCarve& tc, hipStream_t st) {
+    if (hipMemsetAsync(tc.t.claim, 0, tc.bytes, st) != hipSuccess) return YM_ERR_HIP;
+    dim3 ga(unsigned((A + 255) / 256), unsigned(B));
+    hipLaunchKernelGGL(topk_select_kernel<Src>, dim3(unsigned(M), unsigned(B)), dim3(TOPK_THREADS), 0, st, src, A, nc,
+                       gb, gl, valid, M, k, alpha, beta, w, tc.t);
+    hipLaunchKernelGGL(topk_resolve_kernel<Src>, ga, dim3(256), 0, st, src, A, nc, gl, M, alpha, beta, w, tc.t);
+    hipLaunchKernelGGL(topk_norm_kernel, ga, dim3(256), 0, st, A, M, eps, w, tc.t);
+    return YM_OK;
 }
 
 }  // namespace
@@ -854,6 +1039,57 @@ extern "C" int ym_loss_fwd(const float* head, int64_t B, int64_t A, int nc, int 
                        reinterpret_cast<const float4*>(gt_box), gt_lab, M, w);
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, int(nparts), int(B), w);
     YM_LAUNCH_CHECK("ym_loss_fwd");
+    return YM_OK;
+}
+
+// ym_loss_fwd with the top-k assigner: the workspace starts with ym_loss_fwd's carve (ym_loss_bwd and
+// ym_loss_assignment read it as they are), the top-k region follows
+extern "C" size_t ym_loss_topk_workspace_size(int64_t B, int64_t A, int M, int topk) {
+    (void)topk;                                  // the candidate lists live in LDS: no B*M*k table in HBM
+    int64_t nparts = B * ((A + 255) / 256);
+    return carve(nullptr, B, A, M, nparts).bytes + carve_topk(nullptr, B, A, M).bytes + 256;
+}
+
+extern "C" int ym_loss_fwd_topk(const float* head, int64_t B, int64_t A, int nc, int nl, const int* level_h,
+                                const int* level_w, const float* strides, const int64_t* batch_idx, const int64_t* cls,
+                                const float* bboxes, int64_t n_targets, int M, float imgsz_h, float imgsz_w,
+                                void* workspace, size_t workspace_bytes, float* gt_box, float* gt_lab, int* gt_valid,
+                                float* out, int topk, void* stream) {
+    YM_CHECK_ARG(nl >= 1 && nl <= MAXLV, "ym_loss_fwd_topk: 1..4 levels");
+    YM_CHECK_ARG(nc >= 1 && nc <= 1024, "ym_loss_fwd_topk: nc=%d out of range (1..1024)", nc);
+    YM_CHECK_ARG(M >= 0 && M <= 4096, "ym_loss_fwd_topk: M=%d out of range", M);
+    YM_CHECK_ARG(topk >= 1 && topk <= TOPK_MAX, "ym_loss_fwd_topk: topk=%d out of range (1..%d)", topk, TOPK_MAX);
+    YM_CHECK_ARG(B >= 1 && B <= 65535 && A >= 1 && A < (int64_t(1) << 31), "ym_loss_fwd_topk: B=%lld A=%lld",
+                 (long long)B, (long long)A);
+    hipStream_t st = as_stream(stream);
+    Levels L = make_levels(nl, level_h, level_w, strides);
+    YM_CHECK_ARG(L.off[nl] == A, "ym_loss_fwd_topk: level sizes do not sum to A");
+    const int no = 64 + nc;
+    const int64_t nparts = B * ((A + 255) / 256);
+    Carve c = carve(workspace, B, A, M, nparts);
+    TopkCarve tc = carve_topk(static_cast<char*>(workspace) + c.bytes, B, A, M);
+    YM_CHECK_ARG(workspace_bytes >= c.bytes + tc.bytes, "ym_loss_fwd_topk: workspace too small");
+    AssignWs w = c.w;
+    w.out = out;
+    dim3 ga(unsigned((A + 255) / 256), unsigned(B));
+    if (M > 0) {
+        hipLaunchKernelGGL(gt_prep_kernel, dim3(unsigned(B)), dim3(64), 0, st, batch_idx, cls, bboxes,
+                           n_targets, int(B), M, imgsz_h, imgsz_w, reinterpret_cast<float4*>(gt_box), gt_lab, gt_valid);
+        HeadSrc src{head, A, no, L};
+        hipLaunchKernelGGL(topk_decode_kernel, ga, dim3(256), 0, st, src, A, w);
+        int rc = topk_assign(src, B, A, nc, reinterpret_cast<const float4*>(gt_box), gt_lab, gt_valid, M, topk, 0.5f,
+                             4.0f, EPS_TAL, w, tc, st);
+        if (rc != YM_OK) return rc;
+    } else {
+        // no targets in the batch: all background, as ym_loss_fwd
+        if (hipMemsetAsync(w.fg, 0, size_t(B) * A * 4, st) != hipSuccess) return YM_ERR_HIP;
+        if (hipMemsetAsync(w.tgi, 0, size_t(B) * A * 4, st) != hipSuccess) return YM_ERR_HIP;
+        if (hipMemsetAsync(w.norm, 0, size_t(B) * A * 4, st) != hipSuccess) return YM_ERR_HIP;
+    }
+    hipLaunchKernelGGL(loss_partial_kernel, ga, dim3(256), 0, st, head, A, no, nc, L,
+                       reinterpret_cast<const float4*>(gt_box), gt_lab, M, w);
+    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, st, int(nparts), int(B), w);
+    YM_LAUNCH_CHECK("ym_loss_fwd_topk");
     return YM_OK;
 }
 
@@ -992,6 +1228,45 @@ extern "C" int ym_tal_assign(const float* pd_scores, const float* pd_bboxes, con
     hipLaunchKernelGGL(assign_targets_kernel, ga, dim3(256), 0, st, A, nc, gb, gt_labels, M, w, target_labels,
                        reinterpret_cast<float4*>(target_bboxes), target_scores, fg_mask, target_gt_idx);
     YM_LAUNCH_CHECK("ym_tal_assign");
+    return YM_OK;
+}
+
+// TaskAlignedAssigner.forward with the top-k rule on explicit tensors (M >= 1); the same five outputs as
+// ym_tal_assign.  Workspace: the loss carve, the top-k region, the valid flags.
+extern "C" size_t ym_tal_assign_topk_workspace_size(int64_t B, int64_t A, int M, int topk) {
+    return ym_loss_topk_workspace_size(B, A, M, topk) + 256 + size_t(B) * std::max(M, 1) * 4;
+}
+
+extern "C" int ym_tal_assign_topk(const float* pd_scores, const float* pd_bboxes, const float* anc_points,
+                                  const float* gt_labels, const float* gt_bboxes, const float* mask_gt, int64_t B,
+                                  int64_t A, int nc, int M, float alpha, float beta, float eps, void* workspace,
+                                  size_t workspace_bytes, float* target_labels, float* target_bboxes,
+                                  float* target_scores, uint8_t* fg_mask, int64_t* target_gt_idx, int topk,
+                                  void* stream) {
+    YM_CHECK_ARG(M >= 1 && M <= 4096, "ym_tal_assign_topk: M=%d out of range (1..4096)", M);
+    YM_CHECK_ARG(nc >= 1 && nc <= 1024, "ym_tal_assign_topk: nc=%d out of range (1..1024)", nc);
+    YM_CHECK_ARG(topk >= 1 && topk <= TOPK_MAX, "ym_tal_assign_topk: topk=%d out of range (1..%d)", topk, TOPK_MAX);
+    YM_CHECK_ARG(B >= 1 && B <= 65535 && A >= 1 && A < (int64_t(1) << 31), "ym_tal_assign_topk: B=%lld A=%lld",
+                 (long long)B, (long long)A);
+    YM_CHECK_ARG((reinterpret_cast<uintptr_t>(gt_bboxes) & 15) == 0, "ym_tal_assign_topk: gt_bboxes not 16-B aligned");
+    YM_CHECK_ARG((reinterpret_cast<uintptr_t>(target_bboxes) & 15) == 0,
+                 "ym_tal_assign_topk: target_bboxes not 16-B aligned");
+    hipStream_t st = as_stream(stream);
+    const int64_t nparts = B * ((A + 255) / 256);
+    Carve c = carve(workspace, B, A, M, nparts);
+    TopkCarve tc = carve_topk(static_cast<char*>(workspace) + c.bytes, B, A, M);
+    const size_t vbytes = size_t(B) * M * 4;
+    YM_CHECK_ARG(workspace_bytes >= c.bytes + tc.bytes + vbytes, "ym_tal_assign_topk: workspace too small");
+    int* valid = reinterpret_cast<int*>(static_cast<char*>(workspace) + c.bytes + tc.bytes);
+    hipLaunchKernelGGL(mask_valid_kernel, dim3(unsigned((B * M + 255) / 256)), dim3(256), 0, st, mask_gt, B * M, valid);
+    PlainSrc src{pd_scores, pd_bboxes, anc_points, A, nc};
+    const float4* gb = reinterpret_cast<const float4*>(gt_bboxes);
+    int rc = topk_assign(src, B, A, nc, gb, gt_labels, valid, M, topk, alpha, beta, eps, c.w, tc, st);
+    if (rc != YM_OK) return rc;
+    dim3 ga(unsigned((A + 255) / 256), unsigned(B));
+    hipLaunchKernelGGL(assign_targets_kernel, ga, dim3(256), 0, st, A, nc, gb, gt_labels, M, c.w, target_labels,
+                       reinterpret_cast<float4*>(target_bboxes), target_scores, fg_mask, target_gt_idx);
+    YM_LAUNCH_CHECK("ym_tal_assign_topk");
     return YM_OK;
 }
 

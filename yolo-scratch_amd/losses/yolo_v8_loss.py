@@ -8,7 +8,9 @@ target preprocess, task-aligned assignment with the reference's quirks (no
 top-k, sequential forced assignment), CIoU + DFL + BCE and their gradient —
 is libyolomi's ym_loss_fwd / ym_loss_bwd on the (B, A, 64+nc) head buffer.
 The host synchronises once per call (the largest per-image box count sizes
-the GT table) instead of 2*B*M+4 times.
+the GT table) instead of 2*B*M+4 times.  Beside that assignment, and off by
+default, stands the standard top-k task-aligned one (`assigner="topk"`,
+`TaskAlignedAssigner(use_topk=True)`; ym_loss_fwd_topk / ym_tal_assign_topk).
 
 The helper functions (bbox_iou, bbox2dist, make_anchors, dist2bbox) and the
 reference's helper methods (TaskAlignedAssigner.get_pos_mask / get_box_metrics /
@@ -98,14 +100,17 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
 
 
 class TaskAlignedAssigner(nn.Module):
-    """Task-aligned assigner (reference :64-270).  As in the reference, `topk` is stored but never
-    applied.  `forward` runs the HIP assignment kernels of the fused loss (ym_tal_assign)
-    on explicit tensors and returns the reference's 5-tuple; inside v8DetectionLoss the same kernels
-    run fused on the head buffer (ym_loss_fwd)."""
+    """Task-aligned assigner (reference :64-270).  By default (`use_topk=False`) `topk` is stored and not
+    applied, as in the reference: every in-box anchor is a positive.  `forward` runs the HIP
+    assignment kernels of the fused loss (ym_tal_assign) on explicit tensors and returns the reference's
+    5-tuple; inside v8DetectionLoss the same kernels run fused on the head buffer (ym_loss_fwd).
+    `use_topk=True` applies `topk` (1..64): the standard top-k task-aligned rule of DESIGN.md §21
+    (ym_tal_assign_topk), with the same inputs and outputs."""
 
-    def __init__(self, topk=13, num_classes=80, alpha=1.0, beta=6.0, eps=1e-9):
+    def __init__(self, topk=13, num_classes=80, alpha=1.0, beta=6.0, eps=1e-9, use_topk=False):
         super().__init__()
         self.topk, self.num_classes, self.alpha, self.beta, self.eps = topk, num_classes, alpha, beta, eps
+        self.use_topk = bool(use_topk)
 
     @torch.no_grad()
     def forward(self, pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt):
@@ -125,13 +130,22 @@ class TaskAlignedAssigner(nn.Module):
         sc, pb, an = _f32(pd_scores), _f32(pd_bboxes), _f32(anc_points)
         gl, gb = _f32(gt_labels).reshape(B, M), _f32(gt_bboxes).reshape(B, M, 4).clone()   # clone: 16-B aligned
         mg = _f32(mask_gt).reshape(B, M)
-        ws_n = lib().ym_tal_assign_workspace_size(B, A, M)
+        if self.use_topk:
+            ws_n = lib().ym_tal_assign_topk_workspace_size(B, A, M, int(self.topk))
+        else:
+            ws_n = lib().ym_tal_assign_workspace_size(B, A, M)
         ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
         t_lab = torch.empty(B, A, dtype=torch.float32, device=dev)
         t_box = torch.empty(B, A, 4, dtype=torch.float32, device=dev)
         t_sc = torch.empty(B, A, nc, dtype=torch.float32, device=dev)
         fg = torch.empty(B, A, dtype=torch.bool, device=dev)
         tgi = torch.empty(B, A, dtype=torch.int64, device=dev)
+        if self.use_topk:
+            call("ym_tal_assign_topk", sc.data_ptr(), pb.data_ptr(), an.data_ptr(), gl.data_ptr(), gb.data_ptr(),
+                 mg.data_ptr(), B, A, nc, M, float(self.alpha), float(self.beta), float(self.eps), ws.data_ptr(), ws_n,
+                 t_lab.data_ptr(), t_box.data_ptr(), t_sc.data_ptr(), fg.data_ptr(), tgi.data_ptr(), int(self.topk),
+                 stream_ptr(dev))
+            return t_lab.to(gt_labels.dtype), t_box, t_sc, fg, tgi
         call("ym_tal_assign", sc.data_ptr(), pb.data_ptr(), an.data_ptr(), gl.data_ptr(), gb.data_ptr(), mg.data_ptr(),
              B, A, nc, M, float(self.alpha), float(self.beta), float(self.eps), ws.data_ptr(), ws_n, t_lab.data_ptr(), t_box.data_ptr(), t_sc.data_ptr(), fg.data_ptr(),
              tgi.data_ptr(), stream_ptr(dev))
@@ -252,9 +266,12 @@ class BboxLoss(nn.Module):
 class _LossCtx:
     """Per-shape device workspace of the fused loss."""
 
-    def __init__(self, B, A, M, dev):
+    def __init__(self, B, A, M, dev, mode="inbox", topk=0):
         self.B, self.A, self.M = B, A, M
-        self.ws_bytes = lib().ym_loss_workspace_size(B, A, M)
+        if mode == "topk":      # ym_loss_fwd's layout (ym_loss_bwd / ym_loss_assignment read it), then the top-k region
+            self.ws_bytes = lib().ym_loss_topk_workspace_size(B, A, M, topk)
+        else:
+            self.ws_bytes = lib().ym_loss_workspace_size(B, A, M)
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         Mm = max(M, 1)
         self.gt_box = torch.empty(B, Mm, 4, dtype=torch.float32, device=dev)
@@ -279,10 +296,12 @@ class _LossFn(torch.autograd.Function):
         if M is None:
             M = int(torch.bincount(bidx, minlength=B).max().item()) if n else 0
         M = int(M) if n else 0
-        key = (B, A, M)
+        mode = crit.assign_mode
+        topk = int(crit.tal_topk) if mode == "topk" else 0      # tal_topk alone switches nothing on
+        key = (B, A, M, mode, topk)
         lc = crit._ctx.get(key)
         if lc is None:
-            lc = crit._ctx[key] = _LossCtx(B, A, M, dev)
+            lc = crit._ctx[key] = _LossCtx(B, A, M, dev, mode, topk)
         nl = len(level_hw)
         lh = (ctypes.c_int * nl)(*[h for h, _ in level_hw])
         lw = (ctypes.c_int * nl)(*[w for _, w in level_hw])
@@ -291,10 +310,14 @@ class _LossFn(torch.autograd.Function):
         imgsz_w = float(level_hw[0][1] * float(crit.stride[0]))
         st = stream_ptr(dev)
         h = head.detach().contiguous()
-        call("ym_loss_fwd", h.data_ptr(), B, A, nc, nl, lh, lw, strides, bidx.data_ptr() if n else None,
-             cls.data_ptr() if n else None, boxes.data_ptr() if n else None, n, M, imgsz_h, imgsz_w,
-             lc.ws.data_ptr(), lc.ws_bytes, lc.gt_box.data_ptr(), lc.gt_lab.data_ptr(), lc.gt_valid.data_ptr(),
-             lc.out.data_ptr(), st)
+        args = (h.data_ptr(), B, A, nc, nl, lh, lw, strides, bidx.data_ptr() if n else None,
+                cls.data_ptr() if n else None, boxes.data_ptr() if n else None, n, M, imgsz_h, imgsz_w,
+                lc.ws.data_ptr(), lc.ws_bytes, lc.gt_box.data_ptr(), lc.gt_lab.data_ptr(), lc.gt_valid.data_ptr(),
+                lc.out.data_ptr())
+        if mode == "topk":
+            call("ym_loss_fwd_topk", *args, topk, st)
+        else:
+            call("ym_loss_fwd", *args, st)
         ctx.save_for_backward(h)
         ctx.lc, ctx.lv, ctx.strides, ctx.nc = lc, (nl, lh, lw), strides, nc
         crit._last = lc
@@ -319,12 +342,18 @@ class _LossFn(torch.autograd.Function):
 
 
 class v8DetectionLoss:
-    """YOLOv8 detection loss (reference :333-538)."""
+    """YOLOv8 detection loss (reference :333-538).  `assigner="inbox"` (the default) is the reference's
+    assignment: every in-box anchor a positive, `tal_topk` stored and unused.  `assigner="topk"` runs the
+    standard top-k task-aligned assignment with k = `tal_topk` (1..64; DESIGN.md §21) through ym_loss_fwd_topk;
+    everything after the assignment is the same."""
 
-    def __init__(self, model, tal_topk=10):
+    def __init__(self, model, tal_topk=10, assigner="inbox"):
+        if assigner not in ("inbox", "topk"):
+            raise ValueError(f"assigner must be 'inbox' or 'topk', got {assigner!r}")
         self.bce = nn.BCEWithLogitsLoss(reduction="none")
         self.model = model
         self.tal_topk = tal_topk
+        self.assign_mode = assigner
         detect = None
         for m in model.modules():
             if type(m).__name__ == "Detect":
@@ -336,7 +365,8 @@ class v8DetectionLoss:
         self.reg_max = detect.reg_max
         self.stride = detect.stride
         self.device = next(model.parameters()).device
-        self.assigner = TaskAlignedAssigner(topk=50, num_classes=self.nc, alpha=0.5, beta=4.0)
+        self.assigner = TaskAlignedAssigner(topk=tal_topk if assigner == "topk" else 50, num_classes=self.nc, alpha=0.5,
+                                            beta=4.0, use_topk=assigner == "topk")
         self.bbox_loss = BboxLoss(self.reg_max)
         self.epoch = 0
         self.hyp_box = 7.5

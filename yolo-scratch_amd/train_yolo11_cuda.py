@@ -388,6 +388,10 @@ def build_parser():
                          "checkpointed as ema_state_dict")
     ap.add_argument("--ema-decay", type=float, default=0.9999, help="EMA decay once warmed up")
     ap.add_argument("--ema-tau", type=float, default=2000, help="EMA warm-up: decay * (1 - exp(-updates / tau))")
+    ap.add_argument("--assigner", type=str, default="inbox", choices=["inbox", "topk"],
+                    help="inbox: the reference's assignment (every in-box anchor a positive); topk: the standard "
+                         "top-k task-aligned assignment with k = --tal-topk")
+    ap.add_argument("--tal-topk", type=int, default=10, help="k of --assigner topk (1..64); unused with inbox")
     return ap
 
 
@@ -429,7 +433,8 @@ def main():
     if rank0:
         n_params = sum(p.numel() for p in model.parameters())
         print(f"Total parameters: {n_params:,} ({n_params / 1e6:.2f}M)")
-    criterion = v8DetectionLoss(model, tal_topk=10)
+        print(f"Assigner: {args.assigner}, tal_topk: {args.tal_topk}")
+    criterion = v8DetectionLoss(model, tal_topk=args.tal_topk, assigner=args.assigner)
     # the reference's AdamW (:440-451) + clip_grad_norm_(10) (:58-62): on the GPU as yolomi's
     # FusedAdamW (a torch.optim.AdamW with the same state_dict; clipping fused into its step)
     if device.type == "cuda":
