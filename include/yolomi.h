@@ -542,6 +542,32 @@ int ym_resize_linear_u8c(const uint8_t* src, const int64_t* meta, int batch, int
 int ym_augment_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
                    const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out, void* stream);
 
+/* Letterbox: the aspect ratio kept.  Image b is resized (the rule of ym_resize_linear_u8c) to nw x nh pixels and
+ * placed with its first pixel at (left, top) of an out_w x out_h frame whose other pixels are `fill`.  The host
+ * computes the geometry in fp64 (datasets/letterbox.py: letterbox_geometry) and hands it over in this table, one
+ * entry per image, so the device derives nothing:
+ *   r = min(out_h / h0, out_w / w0) (min(r, 1) without scale-up); nw = min(out_w, max(1, floor(w0 r + 0.5))), nh
+ *   likewise; left = (out_w - nw) / 2, top = (out_h - nh) / 2, both floored
+ *   sx = fp32(w0) / fp32(nw), sy = fp32(h0) / fp32(nh), divided on the host: the way back for boxes
+ * An entry with nw, nh, w0 or h0 <= 0, or whose w0 / h0 are not the image's in `meta`, gives an all-fill image. */
+typedef struct ym_lb_entry {
+    int32_t nw, nh;            /* size of the resized image inside the frame */
+    int32_t left, top;         /* frame pixel of its first pixel */
+    int32_t w0, h0;            /* size of the source image */
+    float sx, sy;              /* frame pixels -> source pixels */
+} ym_lb_entry;
+/* src / meta as for ym_resize_linear_u8c (pixel-interleaved, ch = 1..4); out planar (batch, ch, out_h, out_w) fp32:
+ * inside [left, left + nw) x [top, top + nh) the 8-bit resize to (nw, nh) at (x - left, y - top), a copy when
+ * (nw, nh) == (w0, h0); elsewhere float(fill & 255) / 255 in every plane. */
+int ym_letterbox_u8c(const uint8_t* src, const int64_t* meta, const ym_lb_entry* table_dev, int batch, int ch,
+                     int out_h, int out_w, int fill, float* out, void* stream);
+/* Boxes of the letterboxed frame back to source pixels.  boxes (B, N, 4) xyxy normalised to [0, 1] (what the
+ * decode + NMS entry points write), count[b] rows valid in image b.  Rows i < count[b], fp32, every step rounded:
+ *   x' = min(max((x * out_w - left) * sx, 0), w0),  y' = min(max((y * out_h - top) * sy, 0), h0)
+ * Rows i >= count[b] of `out` (B, N, 4) are not written.  boxes and out 16-byte aligned; out may be boxes. */
+int ym_unletterbox_boxes(const float* boxes, const int32_t* count, const ym_lb_entry* table_dev, int64_t B, int64_t N,
+                         int out_h, int out_w, float* out, void* stream);
+
 /* ------------------------------------------------------------------ optimizer tail
  * clip_grad_norm_(params, max_norm) + AdamW.step() over every parameter (train_yolo11_cuda.py:58-62,
  * 440-451).  The parameters form one flat index space: entry e covers elements [offset, offset + n)

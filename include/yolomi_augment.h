@@ -32,6 +32,7 @@
 #endif
 
 static_assert(sizeof(ym_aug_tile) == 88 && sizeof(ym_aug_entry) == 432, "ym_aug_entry layout (yolomi/_lib.py)");
+static_assert(sizeof(ym_lb_entry) == 32, "ym_lb_entry layout (yolomi/_lib.py)");
 
 /* OpenCV resizeGeneric_ coefficients of output index d (see csrc/preprocess.hip) */
 YM_HD static inline void ym_aug_lin_coeff(int d, double scale, int n, int& s, int& a0, int& a1) {
@@ -172,6 +173,36 @@ YM_HD static inline void ym_aug_lin_taps(const uint8_t* im, int h0, int w0, int 
     ym_aug_lin_coeff(x, double(w0) / S, w0, sx, a0, a1);
     ym_aug_lin_coeff(y, double(h0) / S, h0, sy, b0, b1);
     ym_aug_set_taps(im, h0, w0, ch, sx, a0, a1, sy, b0, b1, t);
+}
+
+/* the same for a resize to nw x nh (ym_letterbox_u8c): (x, y) is the pixel of the resized image, 0 <= x < nw,
+ * 0 <= y < nh */
+YM_HD static inline void ym_aug_lin_taps_wh(const uint8_t* im, int h0, int w0, int ch, int nw, int nh, int x, int y,
+                                            ym_aug_taps& t) {
+    int sx, a0, a1, sy, b0, b1;
+    ym_aug_lin_coeff(x, double(w0) / nw, w0, sx, a0, a1);
+    ym_aug_lin_coeff(y, double(h0) / nh, h0, sy, b0, b1);
+    ym_aug_set_taps(im, h0, w0, ch, sx, a0, a1, sy, b0, b1, t);
+}
+
+/* ym_letterbox_u8c: the `ch` values v[0..ch) of frame pixel (x, y) of image b (`e` its table entry) */
+YM_HD static inline void ym_lb_sample_c(const uint8_t* src, const int64_t* meta, int b, int ch, const ym_lb_entry* e,
+                                        int fill, int x, int y, int* v) {
+    const int h0 = int(meta[3 * b + 1]), w0 = int(meta[3 * b + 2]);
+    const bool empty = e->nw <= 0 || e->nh <= 0 || h0 <= 0 || w0 <= 0 || e->h0 != h0 || e->w0 != w0;
+    const int64_t u = int64_t(x) - e->left, w = int64_t(y) - e->top;
+    if (empty || u < 0 || u >= e->nw || w < 0 || w >= e->nh) {
+        for (int c = 0; c < ch; ++c) v[c] = fill & 255;
+        return;
+    }
+    const uint8_t* im = src + meta[3 * b];
+    if (e->nw == w0 && e->nh == h0) {
+        for (int c = 0; c < ch; ++c) v[c] = im[(w * w0 + u) * ch + c];
+        return;
+    }
+    ym_aug_taps t;
+    ym_aug_lin_taps_wh(im, h0, w0, ch, e->nw, e->nh, int(u), int(w), t);
+    for (int c = 0; c < ch; ++c) v[c] = ym_aug_taps_value(t, c);
 }
 
 /* ym_aug_stretch_value's geometry; false: the pixel shows the fill */

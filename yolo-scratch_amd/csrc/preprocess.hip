@@ -24,6 +24,10 @@
 // a loop around that function's pieces: blockIdx.y walks images, so the table entry is block-uniform (scalar loads);
 // each thread produces four consecutive pixels of the flat S * S image and writes them with one 16-byte store
 // (lanes of a wave cover 1 KiB of contiguous output); blockIdx.x grid-strides over the image.
+//
+// Letterbox (ym_letterbox_u8c, ym_unletterbox_boxes): the same launch shape once more, with a per-image
+// table entry (ym_lb_entry) the host computed — the resized size, where it sits in the frame, and the fp32 factors back
+// to source pixels.  The device derives no geometry; the pad takes the fill and reads no source byte.
 #include <algorithm>
 
 #include "common.h"
@@ -167,6 +171,71 @@ __global__ void resize_linear_u8c_kernel(const uint8_t* __restrict__ src, const 
     }
 }
 
+// ym_lb_sample_c (include/yolomi_augment.h) in resize_linear_u8c_kernel's launch shape: out (B, CH, H, W) fp32.
+// blockIdx.y walks images, so the table entry, the image's meta and the copy / resize choice are block-uniform
+// (scalar loads).  A pixel of the pad takes the fill and touches no source byte.
+template <int CH>
+__global__ void letterbox_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                     const ym_lb_entry* __restrict__ table, int batch, int H, int W, float fill,
+                                     int vec, float* __restrict__ out) {
+    const int HW = H * W;
+    const int groups = (HW + 3) >> 2;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const ym_lb_entry e = table[b];
+        const uint8_t* im = src + meta[3 * b];
+        const int h0 = int(meta[3 * b + 1]), w0 = int(meta[3 * b + 2]);
+        const bool empty = e.nw <= 0 || e.nh <= 0 || h0 <= 0 || w0 <= 0 || e.h0 != h0 || e.w0 != w0;
+        const bool copy = e.nw == w0 && e.nh == h0;
+        float* o = out + int64_t(b) * CH * HW;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / W, x = p - y * W;
+            float v[CH][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t u = int64_t(x) - e.left, w = int64_t(y) - e.top;
+                if (p + k < HW && !empty && u >= 0 && u < e.nw && w >= 0 && w < e.nh) {
+                    if (copy) {
+                        const uint8_t* px = im + (w * w0 + u) * CH;
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(px[c]) / 255.0f;
+                    } else {
+                        ym_aug_taps t;
+                        ym_aug_lin_taps_wh(im, h0, w0, CH, e.nw, e.nh, int(u), int(w), t);
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(ym_aug_taps_value(t, c)) / 255.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) v[c][k] = fill;
+                }
+                if (++x == W) { x = 0; ++y; }
+            }
+            store_planes<CH>(o, HW, p, vec, v);
+        }
+    }
+}
+
+// one thread per box; blockIdx.y walks images (entry and count through scalar loads)
+__global__ void unletterbox_boxes_kernel(const float4* __restrict__ boxes, const int32_t* __restrict__ count,
+                                         const ym_lb_entry* __restrict__ table, int batch, int64_t N, float fw,
+                                         float fh, float4* __restrict__ out) {
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const ym_lb_entry e = table[b];
+        const int64_t n = min(int64_t(count[b]), N);
+        const float left = float(e.left), top = float(e.top), w0 = float(e.w0), h0 = float(e.h0);
+        for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
+            const float4 q = boxes[b * N + i];
+            float4 r;
+            r.x = fminf(fmaxf(__fmul_rn(__fsub_rn(__fmul_rn(q.x, fw), left), e.sx), 0.f), w0);
+            r.y = fminf(fmaxf(__fmul_rn(__fsub_rn(__fmul_rn(q.y, fh), top), e.sy), 0.f), h0);
+            r.z = fminf(fmaxf(__fmul_rn(__fsub_rn(__fmul_rn(q.z, fw), left), e.sx), 0.f), w0);
+            r.w = fminf(fmaxf(__fmul_rn(__fsub_rn(__fmul_rn(q.w, fh), top), e.sy), 0.f), h0);
+            out[b * N + i] = r;
+        }
+    }
+}
+
 // ym_aug_sample_c for a block-uniform entry `e` and colour entry `col` (may be null), with augment_pixel's
 // wave-uniform-slot path
 template <int CH>
@@ -283,6 +352,46 @@ extern "C" int ym_resize_linear_u8c(const uint8_t* src, const int64_t* meta, int
     }
 #undef YM_RESIZE_C
     YM_LAUNCH_CHECK("ym_resize_linear_u8c");
+    return YM_OK;
+}
+
+extern "C" int ym_letterbox_u8c(const uint8_t* src, const int64_t* meta, const ym_lb_entry* table_dev, int batch,
+                                int ch, int out_h, int out_w, int fill, float* out, void* stream) {
+    YM_CHECK_ARG(src && meta && table_dev && out && batch >= 0 && out_h > 0 && out_h <= 32768 && out_w > 0 &&
+                     out_w <= 32768 && ch >= 1 && ch <= 4,
+                 "ym_letterbox_u8c: bad arguments (ch is 1..4, out_h and out_w 1..32768)");
+    if (batch == 0) return YM_OK;
+    const int64_t hw = int64_t(out_h) * out_w;
+    const int64_t groups = (hw + 3) / 4;
+    const dim3 grid(unsigned(std::min<int64_t>((groups + 255) / 256, 256)), unsigned(std::min(batch, 65535)));
+    const int vec = hw % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const float fv = float(fill & 255) / 255.0f;
+#define YM_LETTERBOX_C(CH)                                                                                      \
+    hipLaunchKernelGGL(letterbox_u8c_kernel<CH>, grid, dim3(256), 0, as_stream(stream), src, meta, table_dev,   \
+                       batch, out_h, out_w, fv, vec, out)
+    switch (ch) {
+        case 1: YM_LETTERBOX_C(1); break;
+        case 2: YM_LETTERBOX_C(2); break;
+        case 3: YM_LETTERBOX_C(3); break;
+        default: YM_LETTERBOX_C(4); break;
+    }
+#undef YM_LETTERBOX_C
+    YM_LAUNCH_CHECK("ym_letterbox_u8c");
+    return YM_OK;
+}
+
+extern "C" int ym_unletterbox_boxes(const float* boxes, const int32_t* count, const ym_lb_entry* table_dev, int64_t B,
+                                    int64_t N, int out_h, int out_w, float* out, void* stream) {
+    YM_CHECK_ARG(boxes && count && table_dev && out && B >= 0 && B <= INT32_MAX && N >= 0 && out_h > 0 && out_w > 0,
+                 "ym_unletterbox_boxes: bad arguments");
+    YM_CHECK_ARG(reinterpret_cast<uintptr_t>(boxes) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+                 "ym_unletterbox_boxes: boxes and out must be 16-byte aligned");
+    if (B == 0 || N == 0) return YM_OK;
+    const dim3 grid(unsigned(std::min<int64_t>((N + 255) / 256, 1024)), unsigned(std::min<int64_t>(B, 65535)));
+    hipLaunchKernelGGL(unletterbox_boxes_kernel, grid, dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float4*>(boxes), count, table_dev, int(B), N, float(out_w), float(out_h),
+                       reinterpret_cast<float4*>(out));
+    YM_LAUNCH_CHECK("ym_unletterbox_boxes");
     return YM_OK;
 }
 

@@ -4,7 +4,9 @@ CraterDatasetCUDA mirrors /root/reference/yolo_scratch_cuda/datasets/crater_data
 (decode in the workers, stretch-resize on the GPU: datasets/crater.py); collate_fn_cuda mirrors
 :289-346; prepare_batch is the device transfer of train_yolo11_cuda.py:43-45; BatchAugment (datasets/augment.py)
 is the training-time replacement of prepare_batch that augments on the GPU; YoloTxtDataset (datasets/yolo_txt.py)
-reads images/ + labels/*.txt datasets of 1, 3 or 4 planes through the same collate and the same two launches.
+reads images/ + labels/*.txt datasets of 1, 3 or 4 planes through the same collate and the same two launches;
+datasets/letterbox.py keeps the aspect ratio instead of stretching (collate_fn_cuda(letterbox=True)) and maps boxes
+between the source image and the letterboxed frame.
 """
 from .collate import collate_fn_cuda  # noqa: F401
 from .crater import CraterDatasetCUDA, max_gt_count, prepare_batch, resize_batch  # noqa: F401

@@ -107,8 +107,34 @@ def make_entry(tiles, c, centre=None, gain=1.0, fill=114, stretch=False) -> AugE
     return e
 
 
-def plain_entry(src: int, h0: int, w0: int, S: int, inv=None, gain=1.0, fill=114) -> AugEntry:
-    """One stretched image under `inv` (3x3 fp64, output pixel -> canvas pixel; None: identity, flagged)."""
+def letterbox_map(h0: int, w0: int, lb):
+    """Letterboxed-tile pixel index -> source pixel position: the stretch to (nw, nh) after the translation by
+    (-left, -top).  `lb`: (nw, nh, left, top) with nw, nh > 0."""
+    nw, nh, left, top = (int(v) for v in lb)
+    m = np.array([[w0 / nw, 0.0, 0.5 * w0 / nw - 0.5], [0.0, h0 / nh, 0.5 * h0 / nh - 0.5], [0.0, 0.0, 1.0]])
+    return m @ translation(-left, -top)
+
+
+def _letterbox_tile(src: int, h0: int, w0: int, lb, origin, crop, inv) -> AugTile | None:
+    """Tile of a letterboxed image whose frame sits at canvas pixel `origin`: sampled through letterbox_map, owned
+    where the image's interior meets `crop` (canvas, half open); None when the image has no interior."""
+    nw, nh, left, top = (int(v) for v in lb)
+    if nw <= 0 or nh <= 0:
+        return None
+    ox, oy = origin
+    rect = (max(crop[0], ox + left - 0.5), max(crop[1], oy + top - 0.5), min(crop[2], ox + left + nw - 0.5),
+            min(crop[3], oy + top + nh - 0.5))
+    return make_tile(src, letterbox_map(h0, w0, lb) @ translation(-ox, -oy) @ inv, rect)
+
+
+def plain_entry(src: int, h0: int, w0: int, S: int, inv=None, gain=1.0, fill=114, lb=None) -> AugEntry:
+    """One stretched image under `inv` (3x3 fp64, output pixel -> canvas pixel; None: identity, flagged).
+    `lb` (nw, nh, left, top): the image is letterboxed instead; the identity then goes unflagged through the same
+    fixed-point map as every other entry (the flag means the S x S stretch)."""
+    if lb is not None:
+        c = np.eye(3) if inv is None else inv
+        return make_entry([_letterbox_tile(src, h0, w0, lb, (0, 0), (-0.5, -0.5, S - 0.5, S - 0.5), c)], c, None,
+                          gain, fill)
     if inv is None:
         return make_entry([make_tile(src, stretch_map(h0, w0, S), (-0.5, -0.5, S - 0.5, S - 0.5))], np.eye(3), None,
                           gain, fill, stretch=True)
@@ -121,11 +147,15 @@ def mosaic_origins(xc: int, yc: int, S: int):
     return [(xc - S, yc - S), (xc, yc - S), (xc - S, yc), (xc, yc)]
 
 
-def mosaic_entry(srcs, sizes, xc: int, yc: int, S: int, inv, gain=1.0, fill=114) -> AugEntry:
-    """Four stretched tiles (`srcs` batch indices, `sizes` their (h0, w0)) on the 2S canvas around (xc, yc)."""
+def mosaic_entry(srcs, sizes, xc: int, yc: int, S: int, inv, gain=1.0, fill=114, lbs=None) -> AugEntry:
+    """Four stretched tiles (`srcs` batch indices, `sizes` their (h0, w0)) on the 2S canvas around (xc, yc).
+    `lbs`: the tiles' (nw, nh, left, top); they are letterboxed instead and their pad shows the fill."""
     tiles = []
-    for (ox, oy), b, (h0, w0) in zip(mosaic_origins(xc, yc, S), srcs, sizes):
+    for k, ((ox, oy), b, (h0, w0)) in enumerate(zip(mosaic_origins(xc, yc, S), srcs, sizes)):
         rect = (max(ox, 0) - 0.5, max(oy, 0) - 0.5, min(ox + S, 2 * S) - 0.5, min(oy + S, 2 * S) - 0.5)
+        if lbs is not None:
+            tiles.append(_letterbox_tile(b, h0, w0, lbs[k], (ox, oy), rect, inv))
+            continue
         tiles.append(make_tile(b, stretch_map(h0, w0, S) @ translation(-ox, -oy) @ inv, rect))
     return make_entry(tiles, inv, (xc, yc), gain, fill)
 
@@ -263,6 +293,10 @@ class BatchAugment:
         meta = batch["img_meta"].numpy()
         S, B = int(batch["img_size"]), int(meta.shape[0])
         p = self.draw(B, epoch, step)
+        # a letterboxed batch (collate_fn_cuda(letterbox=True)): every tile keeps its aspect ratio; the boxes are
+        # already in the letterboxed frame, so nothing below changes for them
+        geo = batch["img_lb"].numpy() if "img_lb" in batch else None
+        lb_of = (lambda b: geo[b].tolist()) if geo is not None else (lambda b: None)
         bidx = batch["batch_idx"].numpy().reshape(-1)
         boxes = batch["bboxes"].numpy().astype(np.float64).reshape(-1, 4)
         cls = batch["cls"].numpy()
@@ -275,7 +309,7 @@ class BatchAugment:
             A = affine_matrix(S, 2 * S if mosaic else S, p["angle"][i], p["scale"][i], p["shear_x"][i], p["shear_y"][i],
                               p["tx"][i], p["ty"][i])
             if not mosaic and not lr and not ud and np.array_equal(A, np.eye(3)):
-                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, None, gain, self.hyp.fill)
+                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, None, gain, self.hyp.fill, lb=lb_of(i))
                 rows = rows_of[i]
                 o_idx.append(np.full(len(rows), i)), o_cls.append(cls[rows]), o_box.append(boxes[rows])
                 continue
@@ -284,14 +318,14 @@ class BatchAugment:
                 xc, yc = (int(S / 2 + c * S) for c in (p["cx"][i], p["cy"][i]))
                 srcs = [i, *(int(b) for b in p["partners"][i])]
                 table[i] = mosaic_entry(srcs, [(int(meta[b, 1]), int(meta[b, 2])) for b in srcs], xc, yc, S, inv, gain,
-                                        self.hyp.fill)
+                                        self.hyp.fill, lbs=[lb_of(b) for b in srcs] if geo is not None else None)
                 parts = []
                 for (ox, oy), b in zip(mosaic_origins(xc, yc, S), srcs):
                     parts.append(np.clip(boxes[rows_of[b]] * S + np.array([ox, oy, ox, oy], np.float64), 0, 2 * S))
                 canvas_boxes = np.concatenate(parts)
                 rows = np.concatenate([rows_of[b] for b in srcs])
             else:
-                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, inv, gain, self.hyp.fill)
+                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, inv, gain, self.hyp.fill, lb=lb_of(i))
                 rows = rows_of[i]
                 canvas_boxes = boxes[rows] * S
             out, keep = transform_boxes(canvas_boxes, A, S, lr, ud)

@@ -112,10 +112,12 @@ class CraterDatasetCUDA(torch.utils.data.Dataset):
         return img, boxes, labels, idx
 
 
-def pack_images(imgs, img_size: int, channels: int = 1):
+def pack_images(imgs, img_size: int, channels: int = 1, letterbox: bool = False):
     """Raw uint8 images -> one pinned byte buffer + meta (B, 3) int64 {offset, h, w}.  channels == 1: (1, h, w)
     images; channels > 1: pixel-interleaved (h, w, channels) images, as the decoder yields them (offsets count
-    h * w * channels bytes), and the dict also carries "img_ch"."""
+    h * w * channels bytes), and the dict also carries "img_ch".  `letterbox`: the dict also carries "img_lb",
+    (B, 4) int32 rows (nw, nh, left, top) of datasets.letterbox.letterbox_geometry, and prepare_batch letterboxes
+    the images instead of stretching them."""
     channels = int(channels)
     if not 1 <= channels <= 4:
         raise ValueError(f"pack_images: channels must be 1..4, got {channels}")
@@ -140,6 +142,9 @@ def pack_images(imgs, img_size: int, channels: int = 1):
     out = {"img_u8": buf, "img_meta": meta, "img_size": int(img_size)}
     if channels > 1:
         out["img_ch"] = channels
+    if letterbox:
+        from .letterbox import geometry_of
+        out["img_lb"] = torch.from_numpy(geometry_of(meta, int(img_size), int(img_size)))
     return out
 
 
@@ -177,6 +182,16 @@ def prepare_batch(batch: dict, device) -> dict:
         out["max_gt"] = max_gt_count(bidx)
     for k, v in batch.items():
         out[k] = v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v
-    if "img_u8" in out:
+    if "img_u8" in out and "img_lb" in out:
+        # a letterboxed batch (collate_fn_cuda(letterbox=True)): the geometry rows travel in a table of ym_lb_entry
+        from .letterbox import letterbox_batch, table_bytes, table_of
+        tb = table_bytes(table_of(batch["img_meta"], batch["img_lb"]), int(batch["img_meta"].shape[0]))
+        if torch.device(device).type == "cuda":
+            tb = tb.pin_memory()
+        out.pop("img_lb")
+        S = out.pop("img_size")
+        out["img"] = letterbox_batch(out.pop("img_u8"), out.pop("img_meta"), tb.to(device, non_blocking=True), S, S,
+                                     out.pop("img_ch", 1))
+    elif "img_u8" in out:
         out["img"] = resize_batch(out.pop("img_u8"), out.pop("img_meta"), out.pop("img_size"), out.pop("img_ch", 1))
     return out

@@ -1,0 +1,105 @@
+"""Run a trained YOLOv11 on image files (MI355X): boxes in each image's own pixels.
+
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --scale s --ch 3 --nc 80 --ema
+
+Per image `<save-dir>/<stem>.txt` with rows `cls cx cy w h conf` normalised to the source image (the label format of
+datasets/yolo_txt.py plus the confidence), and one `<save-dir>/predictions.json` with the pixel boxes.  The images
+are decoded on the host, letterboxed on the GPU, and everything up to the source-pixel boxes stays there
+(yolomi/predict.py); the model is built and the checkpoint loaded as the trainer does it.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).parent))
+
+import train_yolo11_cuda as T  # noqa: E402
+from datasets.yolo_txt import IMG_EXTS  # noqa: E402
+from yolomi.predict import Predictor  # noqa: E402
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="YOLOv11 inference on image files (MI355X)")
+    ap.add_argument("--weights", type=str, required=True, help="last.pt / best.pt written by train_yolo11_cuda.py")
+    ap.add_argument("--source", type=str, required=True, help="an image file, or a directory searched recursively")
+    ap.add_argument("--cfg", type=str, default=str(Path(__file__).parent / "configs" / "yolo11n_crater.yaml"))
+    ap.add_argument("--scale", type=str, default="s", choices=["n", "s", "m", "l", "x"])
+    ap.add_argument("--ch", type=int, default=1, choices=[1, 3, 4], help="image planes: 1 (luma), 3 (RGB) or 4 (RGBA)")
+    ap.add_argument("--nc", type=int, default=5, help="number of classes")
+    ap.add_argument("--imgsz", type=int, default=640)
+    ap.add_argument("--batch", type=int, default=8, help="images per forward; the last batch is padded to it")
+    ap.add_argument("--conf", type=float, default=0.25)
+    ap.add_argument("--iou", type=float, default=0.45)
+    ap.add_argument("--max-det", type=int, default=300, help="boxes kept per image (0: no cap)")
+    ap.add_argument("--ema", action="store_true", help="load the averaged weights (ema_state_dict) when present")
+    ap.add_argument("--save-dir", type=str, default="runs/predict")
+    return ap
+
+
+def find_images(source):
+    p = Path(source)
+    if p.is_dir():
+        return sorted(f for f in p.rglob("*") if f.is_file() and f.suffix.lower() in IMG_EXTS)
+    if p.is_file():
+        return [p]
+    raise FileNotFoundError(f"--source {source}: no such file or directory")
+
+
+def read_image(path, ch):
+    """uint8 (h, w) for one plane (the crater loader's luma), (h, w, ch) otherwise, as the datasets decode."""
+    if ch == 1:
+        from datasets.crater import _gray_u8
+        return _gray_u8(str(path))
+    from PIL import Image
+    with Image.open(path) as f:
+        return np.array(f.convert({3: "RGB", 4: "RGBA"}[ch]), dtype=np.uint8)
+
+
+def txt_rows(det, h0, w0):
+    """`cls cx cy w h conf` rows, normalised to the h0 x w0 source image."""
+    rows = []
+    for (x1, y1, x2, y2), s, c in zip(det["boxes"].tolist(), det["scores"].tolist(), det["labels"].tolist()):
+        rows.append(f"{int(c)} {(x1 + x2) / 2 / w0:.6f} {(y1 + y2) / 2 / h0:.6f} {(x2 - x1) / w0:.6f} "
+                    f"{(y2 - y1) / h0:.6f} {s:.6f}")
+    return rows
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("yolomi runs on MI355X GPUs only (no CPU fallback)")
+    device = torch.device("cuda", 0)
+    files = find_images(args.source)
+    if not files:
+        raise SystemExit(f"--source {args.source}: no images")
+    model = T.build_model(args.cfg, args.scale, args.ch, args.nc, device)
+    key = T.load_checkpoint(args.weights, model, device, ema=args.ema)
+    print(f"Loaded {key} from {args.weights}")
+    predictor = Predictor(model, imgsz=args.imgsz, ch=args.ch, conf=args.conf, iou=args.iou, max_det=args.max_det,
+                          class_aware=True, device=device, batch=args.batch)
+    save_dir = Path(args.save_dir)
+    save_dir.mkdir(parents=True, exist_ok=True)
+    results = []
+    for lo in range(0, len(files), args.batch):
+        chunk = files[lo:lo + args.batch]
+        images = [read_image(f, args.ch) for f in chunk]
+        for f, im, det in zip(chunk, images, predictor(images)):
+            det = {k: v.cpu() for k, v in det.items()}
+            h0, w0 = im.shape[:2]
+            (save_dir / f"{f.stem}.txt").write_text("".join(r + "\n" for r in txt_rows(det, h0, w0)))
+            results.append({"image": str(f), "height": h0, "width": w0, "boxes": det["boxes"].tolist(),
+                            "scores": det["scores"].tolist(), "labels": det["labels"].tolist()})
+    (save_dir / "predictions.json").write_text(json.dumps({"weights": str(args.weights), "state": key,
+                                                           "imgsz": args.imgsz, "conf": args.conf, "iou": args.iou,
+                                                           "images": results}))
+    print(f"{len(results)} images, {sum(len(r['scores']) for r in results)} boxes -> {save_dir}")
+
+
+if __name__ == "__main__":
+    main()

@@ -256,6 +256,15 @@ def _load_np_safe(path, device):
         return torch.load(path, map_location=device, weights_only=True)
 
 
+def load_checkpoint(path, model, device, ema=False):
+    """Weights of a last.pt / best.pt into `model`, for inference -> the key they came from.  `ema`: the averaged
+    weights ("ema_state_dict") when the checkpoint holds them, else (and without `ema`) "model_state_dict"."""
+    ckpt = _load_np_safe(path, device)
+    key = "ema_state_dict" if ema and "ema_state_dict" in ckpt else "model_state_dict"
+    model.load_state_dict(ckpt[key])
+    return key
+
+
 def resume_checkpoint(path, model, optimizer, device, ema=None):
     """Resume as the reference does (:576-586) -> (start_epoch, best_loss, best_mAP50).  Loaded with
     weights_only=True plus the numpy scalar types a reference-written checkpoint holds (its metrics
@@ -276,13 +285,14 @@ def resume_checkpoint(path, model, optimizer, device, ema=None):
     return ckpt["epoch"] + 1, ckpt.get("best_loss", float("inf")), ckpt.get("best_mAP50", 0.0)
 
 
-def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None, channels=1):
+def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None, channels=1, letterbox=False):
     """The reference's split and loaders (:491-543): seed-42 permutation, Subset train / val,
     shuffled train loader, ordered val loader, drop_last=False.  Under data parallelism the train set
     is sharded by a DistributedSampler(shuffle=True, drop_last=True): every rank gets the same number
     of samples and so the same number of batches (a rank with one batch more would enter the gradient
     all-reduce alone and hang), reshuffled every epoch (set_epoch); the val set by ValShard (no
-    padding: no image counted twice).  `channels`: the dataset's image planes, handed to the collate.
+    padding: no image counted twice).  `channels`: the dataset's image planes, handed to the collate; `letterbox`:
+    both loaders keep the images' aspect ratio (datasets/letterbox.py) instead of stretching them.
     -> (train_loader, val_loader, train_sampler or None)."""
     import functools
     from torch.utils.data import DataLoader, DistributedSampler, Subset
@@ -291,7 +301,8 @@ def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate
     idx = torch.randperm(n, generator=torch.Generator().manual_seed(42)).tolist()
     tr, va = Subset(dataset, idx[: n - val_size]), Subset(dataset, idx[n - val_size:])
     nw = min(workers, 4)
-    col = collate or functools.partial(collate_fn, img_size=imgsz, channels=channels)
+    col = collate or (functools.partial(collate_fn, img_size=imgsz, channels=channels, letterbox=True) if letterbox
+                      else functools.partial(collate_fn, img_size=imgsz, channels=channels))
     kw = dict(batch_size=batch, num_workers=nw, collate_fn=col, pin_memory=torch.cuda.is_available(),
               persistent_workers=nw > 0, prefetch_factor=2 if nw > 0 else None, drop_last=False)
     if dp_ctx is not None and dp_ctx.world > 1:
@@ -332,9 +343,20 @@ class _Parser(argparse.ArgumentParser):
                        "yolo)")
         if ns.data_format == "yolo" and ns.ch not in (1, 3, 4):
             self.error("--data-format yolo decodes to 1 (luma), 3 (RGB) or 4 (RGBA) planes")
+        if ns.letterbox and ns.synthetic:
+            self.error("--letterbox acts on a dataset's images: synthetic batches are generated at --imgsz")
         if not 1 <= ns.ch <= 4 or ns.nc < 1:
             self.error("--ch is 1..4 and --nc at least 1")
         return ns, rest
+
+
+def build_model(cfg, scale, ch, nc, device):
+    """The model of a yaml file at one scale, on the device (main's and predict.py's builder)."""
+    import yaml
+    with open(cfg) as f:
+        cfg_dict = yaml.safe_load(f)
+    cfg_dict["scale"] = scale
+    return build_yolo11(cfg=cfg_dict, ch=ch, nc=nc).to(device)
 
 
 def build_parser():
@@ -392,6 +414,9 @@ def build_parser():
                     help="inbox: the reference's assignment (every in-box anchor a positive); topk: the standard "
                          "top-k task-aligned assignment with k = --tal-topk")
     ap.add_argument("--tal-topk", type=int, default=10, help="k of --assigner topk (1..64); unused with inbox")
+    ap.add_argument("--letterbox", action="store_true",
+                    help="keep the images' aspect ratio in the train and val loaders (resize + centred pad on the GPU, "
+                         "datasets/letterbox.py) instead of stretching them to --imgsz; metrics stay in that frame")
     return ap
 
 
@@ -423,13 +448,10 @@ def main():
             from datasets import CraterDatasetCUDA
             dataset = CraterDatasetCUDA(args.data, img_size=args.imgsz, cache_images=False, augment=True)
         train_loader, val_loader, train_sampler = make_loaders(dataset, args.val_split, args.batch, args.workers,
-                                                               args.imgsz, dp_ctx, channels=args.ch)
+                                                               args.imgsz, dp_ctx, channels=args.ch,
+                                                               letterbox=args.letterbox)
 
-    import yaml
-    with open(args.cfg) as f:
-        cfg_dict = yaml.safe_load(f)
-    cfg_dict["scale"] = args.scale
-    model = build_yolo11(cfg=cfg_dict, ch=args.ch, nc=args.nc).to(device)
+    model = build_model(args.cfg, args.scale, args.ch, args.nc, device)
     if rank0:
         n_params = sum(p.numel() for p in model.parameters())
         print(f"Total parameters: {n_params:,} ({n_params / 1e6:.2f}M)")

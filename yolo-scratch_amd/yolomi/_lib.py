@@ -72,6 +72,12 @@ class AugColour(ctypes.Structure):
     _fields_ = [("hue", I32), ("sat", I32)]
 
 
+class LbEntry(ctypes.Structure):
+    """ym_lb_entry (include/yolomi.h): per-image letterbox geometry, computed on the host."""
+    _fields_ = [("nw", I32), ("nh", I32), ("left", I32), ("top", I32), ("w0", I32), ("h0", I32), ("sx", F32),
+                ("sy", F32)]
+
+
 R = _c.c_int
 # name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (the setters of the kernel
 # variants measured and rejected in rounds 5 / 6 went with their code: DESIGN §12 / §13, profiles/r05, profiles/r06; the code
@@ -184,6 +190,8 @@ SIGNATURES = {
     "ym_augment_u8": (R, [P, P, P, INT, INT, P, P]),
     "ym_resize_linear_u8c": (R, [P, P, INT, INT, INT, P, P]),
     "ym_augment_u8c": (R, [P, P, P, P, INT, INT, INT, P, P]),
+    "ym_letterbox_u8c": (R, [P, P, P, INT, INT, INT, INT, INT, P, P]),
+    "ym_unletterbox_boxes": (R, [P, P, P, I64, I64, INT, INT, P, P]),
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),

@@ -53,12 +53,16 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float, labels:
 
 
 def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_aware: bool = False,
-               max_det: int = 0):
+               max_det: int = 0, padded: bool = False):
     """Batched decode+NMS of pred read as (B, N, 4+C).  Returns per-image dicts.
 
     `class_aware`: a candidate is suppressed by kept candidates of its own label only; `max_det` > 0: at most that
     many boxes per image, the best-scoring kept ones (ym_decode_nms_cls).  With the defaults: the
-    reference's class-agnostic NMS (ym_decode_nms_strided)."""
+    reference's class-agnostic NMS (ym_decode_nms_strided).
+
+    `padded`: one dict for the batch instead of the list: boxes (B, N, 4), scores / labels (B, N), "count" the
+    per-image counts on the device (int32) and "counts" the same on the host; rows past an image's count are
+    unspecified (what datasets.letterbox.unletterbox takes)."""
     require_device(pred)
     from ._lib import lib
     p = pred.float()
@@ -86,4 +90,6 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
              float(iou_thr), float(img_size), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores), ptr(labels),
              ptr(index), stream_ptr(dev))
     counts = cnt.cpu().tolist()                      # the single host sync of the batch
+    if padded:
+        return {"boxes": boxes, "scores": scores, "labels": labels, "count": cnt, "counts": counts}
     return [{"boxes": boxes[b, :k], "scores": scores[b, :k], "labels": labels[b, :k]} for b, k in enumerate(counts)]

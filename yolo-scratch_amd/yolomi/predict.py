@@ -1,0 +1,84 @@
+"""From images to detections in the images' own pixels.
+
+Predictor chains four device steps per batch, none of which leaves the GPU:
+  pack + ym_letterbox_u8c    the raw uint8 images -> (B, ch, S, S) fp32, the aspect ratio kept
+  eval forward               the model's one-launch eval graph (yolomi/graph.py); the batch is padded with empty
+                             images to a fixed size, so the captured graph replays for every batch, the last included
+  decode + NMS               yolomi.post.decode_nms on the anchor-major view (labels are classes)
+  ym_unletterbox_boxes       kept boxes -> source-pixel xyxy through the same geometry table
+The host synchronises once per batch, for the per-image counts.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import post as _post
+from ._lib import YolomiError
+
+
+class Predictor:
+    """predictor(images) -> per image {"boxes" (n, 4) fp32 xyxy in source pixels, "scores" (n,), "labels" (n,)}, on
+    the device.  `images`: uint8 arrays (or tensors), (h, w, ch) — (h, w) also for one plane.  `class_aware`: NMS
+    within a class, at most `max_det` boxes per image (0: no cap); without it the class-agnostic NMS, which has no
+    cap.  `batch`: the fixed batch size of the forward; more images run in several batches."""
+
+    def __init__(self, model, imgsz: int = 640, ch: int | None = None, conf: float = 0.25, iou: float = 0.45,
+                 max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise YolomiError("Predictor runs on the MI355X only (no CPU fallback)")
+        self.model = model.to(self.device).eval()
+        stem = int(model.model[0].conv.in_channels)
+        self.ch = stem if ch is None else int(ch)
+        if self.ch != stem:
+            raise ValueError(f"Predictor: ch={self.ch} but the model's stem takes {stem} planes")
+        self.imgsz, self.conf, self.iou = int(imgsz), float(conf), float(iou)
+        self.max_det, self.class_aware, self.batch, self.fill = int(max_det), bool(class_aware), int(batch), int(fill)
+        if self.batch < 1 or self.imgsz < 1:
+            raise ValueError("Predictor: batch and imgsz are at least 1")
+
+    def _raw(self, im) -> torch.Tensor:
+        """One image in the layout pack_images takes: (1, h, w) for one plane, (h, w, ch) otherwise."""
+        t = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im.cpu().contiguous()
+        if t.dtype != torch.uint8:
+            raise ValueError(f"Predictor: images are uint8, got {t.dtype}")
+        if self.ch == 1 and t.dim() == 3 and t.shape[-1] == 1:
+            t = t[..., 0]
+        if self.ch == 1 and t.dim() == 2:
+            return t.unsqueeze(0)
+        if self.ch > 1 and t.dim() == 3 and t.shape[-1] == self.ch:
+            return t
+        raise ValueError(f"Predictor: expected (h, w{', ' + str(self.ch) if self.ch > 1 else ''}) uint8 images, got "
+                         f"{tuple(t.shape)}")
+
+    def letterbox(self, images):
+        """pack + ym_letterbox_u8c of up to `batch` images, padded with empty ones -> (img (batch, ch, S, S) on the
+        device, the device table of ym_lb_entry)."""
+        from datasets.crater import pack_images
+        from datasets.letterbox import lb_table, letterbox_batch, table_bytes
+        raw = [self._raw(im) for im in images]
+        empty = torch.empty((1, 0, 0) if self.ch == 1 else (0, 0, self.ch), dtype=torch.uint8)
+        raw += [empty] * (self.batch - len(raw))
+        packed = pack_images(raw, self.imgsz, self.ch)
+        S = self.imgsz
+        tb = table_bytes(lb_table(packed["img_meta"], S, S), self.batch).pin_memory()
+        mv = lambda t: t.to(self.device, non_blocking=True)          # noqa: E731
+        table = mv(tb)
+        return letterbox_batch(mv(packed["img_u8"]), mv(packed["img_meta"]), table, S, S, self.ch, self.fill), table
+
+    @torch.no_grad()
+    def _run(self, images):
+        from datasets.letterbox import unletterbox
+        img, table = self.letterbox(images)
+        y = self.model(img)[0]                                       # (batch, 4 + nc, A)
+        dets = _post.decode_nms(y.transpose(1, 2), self.imgsz, self.conf, self.iou, class_aware=self.class_aware,
+                                max_det=self.max_det if self.class_aware else 0, padded=True)
+        return unletterbox(dets, table, self.imgsz, self.imgsz)[:len(images)]
+
+    def __call__(self, images):
+        images = list(images)
+        out = []
+        for lo in range(0, len(images), self.batch):
+            out += self._run(images[lo:lo + self.batch])
+        return out
