@@ -77,6 +77,14 @@ int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, int64_t C, in
                           int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_size,
                           void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
                           float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream);
+/* The same for a frame of img_h rows and img_w columns (rectangular inference): kept boxes are written as
+ * x / img_w, y / img_h, each clamped to [0, 1]; suppression runs on the pixel boxes and is ym_decode_nms_strided's.
+ * img_w = img_h = img_size is ym_decode_nms_strided bit for bit.  img_w <= 0 or img_h <= 0: YM_ERR_ARG. */
+int ym_decode_nms_strided_wh(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
+                             int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_w,
+                             float img_h, void* workspace, size_t workspace_bytes, int32_t* out_count,
+                             float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
+                             void* stream);
 
 /* nms_simple (train_yolo11_cuda.py:361-399) on one set of n xyxy boxes:
  * keep[0..*count) are indices into boxes in kept (score-descending) order. */
@@ -94,6 +102,11 @@ int ym_decode_nms_cls(const float* pred, int64_t B, int64_t N, int64_t C, int64_
                       int64_t col_stride, float conf, float iou_thr, float img_size, int max_det, void* workspace,
                       size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
                       int64_t* out_labels, int64_t* out_index, void* stream);
+/* ym_decode_nms_cls for a frame of img_h rows and img_w columns, as ym_decode_nms_strided_wh. */
+int ym_decode_nms_cls_wh(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride, int64_t img_stride,
+                         int64_t col_stride, float conf, float iou_thr, float img_w, float img_h, int max_det,
+                         void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                         float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream);
 /* ym_nms with one label per box (any int64 values, compared for equality only; NULL: one class) and the cap:
  * a batched NMS.  Workspace: ym_nms_cls_workspace_size(1, n). */
 int ym_nms_cls(const float* boxes, const float* scores, const int64_t* labels, int64_t n, float iou_thr, int max_det,

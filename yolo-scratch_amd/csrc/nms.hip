@@ -17,7 +17,7 @@
 //        c. greedy loop: the head box is broadcast through LDS, every thread
 //           tests the boxes it holds in registers, drops IoU > thr, and a
 //           block min-reduction finds the next alive head        (:380-397)
-//        d. write kept boxes / img_size clamped to [0,1]          (:342-350)
+//        d. write kept boxes / (img_w, img_h) clamped to [0,1]          (:342-350)
 #include <cstdlib>
 
 #include "common.h"
@@ -244,7 +244,7 @@ __device__ void bitonic(uint64_t* keys, int P) {
 // the label compared, equality only) and the max_det cap (0: none).  The CLS = false instances ignore both.
 template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t>
 __global__ void __launch_bounds__(NMS_THREADS)
-nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp_norm, Ws w,
+nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h, int clamp_norm, Ws w,
                  int32_t* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                  int64_t* __restrict__ out_labels, int64_t* __restrict__ out_index,
                  const LT* __restrict__ labs = nullptr, int max_det = 0) {
@@ -415,10 +415,10 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_size, int clamp
         int64_t row = base + w.frow[base + f];
         float4 bx = w.box[row];
         if (clamp_norm) {
-            bx.x = fminf(fmaxf(bx.x / img_size, 0.0f), 1.0f);
-            bx.y = fminf(fmaxf(bx.y / img_size, 0.0f), 1.0f);
-            bx.z = fminf(fmaxf(bx.z / img_size, 0.0f), 1.0f);
-            bx.w = fminf(fmaxf(bx.w / img_size, 0.0f), 1.0f);
+            bx.x = fminf(fmaxf(bx.x / img_w, 0.0f), 1.0f);
+            bx.y = fminf(fmaxf(bx.y / img_h, 0.0f), 1.0f);
+            bx.z = fminf(fmaxf(bx.z / img_w, 0.0f), 1.0f);
+            bx.w = fminf(fmaxf(bx.w / img_h, 0.0f), 1.0f);
         }
         int64_t o = base + k;
         reinterpret_cast<float4*>(out_boxes)[o] = bx;
@@ -552,7 +552,8 @@ constexpr int SCAN_RB = 8;                          // kept rows per group gathe
 // CAP: stop at max_det (> 0) kept boxes: the chunk whose alive bits would pass the cap keeps its lowest
 // max_det - nkept of them (sorted order within a chunk is bit order) and the scan ends; later decisions cannot matter.
 template <bool CAP>
-__global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP, int Wn, float img_size, Ws w,
+__global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP, int Wn, float img_w, float img_h,
+                                                           Ws w,
                                                            int32_t* __restrict__ out_count,
                                                            float* __restrict__ out_boxes,
                                                            float* __restrict__ out_scores,
@@ -715,10 +716,10 @@ __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP
         const int f = int(uint32_t(w.keys[b * KP + spos]));
         const int64_t row = base + w.frow[base + f];
         float4 bx = w.box[row];
-        bx.x = fminf(fmaxf(bx.x / img_size, 0.0f), 1.0f);
-        bx.y = fminf(fmaxf(bx.y / img_size, 0.0f), 1.0f);
-        bx.z = fminf(fmaxf(bx.z / img_size, 0.0f), 1.0f);
-        bx.w = fminf(fmaxf(bx.w / img_size, 0.0f), 1.0f);
+        bx.x = fminf(fmaxf(bx.x / img_w, 0.0f), 1.0f);
+        bx.y = fminf(fmaxf(bx.y / img_h, 0.0f), 1.0f);
+        bx.z = fminf(fmaxf(bx.z / img_w, 0.0f), 1.0f);
+        bx.w = fminf(fmaxf(bx.w / img_h, 0.0f), 1.0f);
         reinterpret_cast<float4*>(out_boxes)[base + k] = bx;
         out_scores[base + k] = w.score[row];
         out_labels[base + k] = w.label[row];
@@ -729,7 +730,7 @@ __global__ void __launch_bounds__(64) nms_scan_wave_kernel(int64_t N, int64_t KP
 
 // cls: the class-aware instances with the max_det cap (0: none); lab64: the caller's 64-bit labels by row (ym_nms_cls),
 // null: w.label.  The class-agnostic entry points launch the CLS = false / CAP = false instances.
-int launch_nms(int64_t B, int64_t Nalloc, float iou_thr, float img_size, int clamp_norm, Ws w,
+int launch_nms(int64_t B, int64_t Nalloc, float iou_thr, float img_w, float img_h, int clamp_norm, Ws w,
                int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
                hipStream_t st, bool cls = false, int max_det = 0, const int64_t* lab64 = nullptr) {
     size_t lds = size_t(SORT_LDS_KEYS) * sizeof(uint64_t);
@@ -738,8 +739,8 @@ int launch_nms(int64_t B, int64_t Nalloc, float iou_thr, float img_size, int cla
         const int64_t KP = pow2_at_least(Nalloc);
         // (the compaction never reads a label: one instance serves both)
         hipLaunchKernelGGL((nms_image_kernel<true, false, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
-                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
-                           out_index, static_cast<const int32_t*>(nullptr), 0);
+                           Nalloc, KP, iou_thr, img_w, img_h, clamp_norm, w, out_count, out_boxes, out_scores,
+                           out_labels, out_index,static_cast<const int32_t*>(nullptr), 0);
         const unsigned nt = unsigned((Nalloc + 255) / 256);
         hipLaunchKernelGGL(nms_rank_kernel, dim3(nt, nt, unsigned(B)), dim3(256), 0, st, Nalloc, w);
         const dim3 mgrid(unsigned(Wn * (Wn + 1) / 2), 1, unsigned(B));
@@ -751,27 +752,27 @@ int launch_nms(int64_t B, int64_t Nalloc, float iou_thr, float img_size, int cla
             hipLaunchKernelGGL(nms_mask_kernel<false>, mgrid, dim3(64), 0, st, Nalloc, Wn, iou_thr, w);
         }
         if (cls && max_det > 0)
-            hipLaunchKernelGGL(nms_scan_wave_kernel<true>, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn, img_size,
-                               w, out_count, out_boxes, out_scores, out_labels, out_index, max_det);
+            hipLaunchKernelGGL(nms_scan_wave_kernel<true>, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn, img_w,
+                               img_h, w, out_count, out_boxes, out_scores, out_labels, out_index, max_det);
         else
             hipLaunchKernelGGL(nms_scan_wave_kernel<false>, dim3(unsigned(B)), dim3(64), 0, st, Nalloc, KP, Wn,
-                               img_size, w, out_count, out_boxes, out_scores, out_labels, out_index, 0);
+                               img_w, img_h, w, out_count, out_boxes, out_scores, out_labels, out_index, 0);
         YM_LAUNCH_CHECK("nms bitmask path");
         return YM_OK;
     }
     const int64_t KP = pow2_at_least(Nalloc);
     if (cls && lab64)
         hipLaunchKernelGGL((nms_image_kernel<false, true, int64_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
-                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
-                           out_index, lab64, max_det);
+                           Nalloc, KP, iou_thr, img_w, img_h, clamp_norm, w, out_count, out_boxes, out_scores,
+                           out_labels, out_index,lab64, max_det);
     else if (cls)
         hipLaunchKernelGGL((nms_image_kernel<false, true, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
-                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
-                           out_index, static_cast<const int32_t*>(w.label), max_det);
+                           Nalloc, KP, iou_thr, img_w, img_h, clamp_norm, w, out_count, out_boxes, out_scores,
+                           out_labels, out_index,static_cast<const int32_t*>(w.label), max_det);
     else
         hipLaunchKernelGGL((nms_image_kernel<false, false, int32_t>), dim3(unsigned(B)), dim3(NMS_THREADS), lds, st,
-                           Nalloc, KP, iou_thr, img_size, clamp_norm, w, out_count, out_boxes, out_scores, out_labels,
-                           out_index, static_cast<const int32_t*>(nullptr), 0);
+                           Nalloc, KP, iou_thr, img_w, img_h, clamp_norm, w, out_count, out_boxes, out_scores,
+                           out_labels, out_index,static_cast<const int32_t*>(nullptr), 0);
     YM_LAUNCH_CHECK("nms_image_kernel");
     return YM_OK;
 }
@@ -798,10 +799,11 @@ extern "C" int ym_iou_row(const float* box1, const float* boxes2, int64_t m, flo
     return YM_OK;
 }
 
-// cls: ym_decode_nms_cls (its workspace layout, the class-aware kernels, the max_det cap)
+// cls: ym_decode_nms_cls (its workspace layout, the class-aware kernels, the max_det cap).  Kept boxes are written as
+// x / img_w, y / img_h; the single-size entry points pass img_w = img_h = img_size.
 static int decode_nms_impl(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride, int64_t img_stride,
-                           int64_t col_stride, float conf, float iou_thr, float img_size, bool cls, int max_det,
-                           void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                           int64_t col_stride, float conf, float iou_thr, float img_w, float img_h, bool cls,
+                           int max_det, void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
                            float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream) {
     YM_CHECK_ARG(max_det >= 0, "ym_decode_nms_cls: max_det %d < 0", max_det);
     YM_CHECK_ARG(B >= 0 && N >= 0 && C >= 1, "ym_decode_nms: bad shape B=%lld N=%lld C=%lld", (long long)B,
@@ -821,15 +823,28 @@ static int decode_nms_impl(const float* pred, int64_t B, int64_t N, int64_t C, i
         hipLaunchKernelGGL(rowmax_wave_kernel, dim3(unsigned((B * N + 3) / 4)), dim3(256), 0, st, pred, B, N, C,
                            row_stride, img_stride, col_stride, conf, w);
     YM_LAUNCH_CHECK("rowmax");
-    return launch_nms(B, N, iou_thr, img_size, 1, w, out_count, out_boxes, out_scores, out_labels, out_index, st, cls,
-                      max_det);
+    return launch_nms(B, N, iou_thr, img_w, img_h, 1, w, out_count, out_boxes, out_scores, out_labels, out_index, st,
+                      cls, max_det);
 }
 
 extern "C" int ym_decode_nms_strided(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
                                      int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_size,
                                      void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
                                      float* out_scores, int64_t* out_labels, int64_t* out_index, void* stream) {
-    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, false, 0,
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, img_size, false,
+                           0, workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                           stream);
+}
+
+// A frame of img_h rows and img_w columns: x / img_w, y / img_h.  Everything else is ym_decode_nms_strided.
+extern "C" int ym_decode_nms_strided_wh(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
+                                        int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_w,
+                                        float img_h, void* workspace, size_t workspace_bytes, int32_t* out_count,
+                                        float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
+                                        void* stream) {
+    YM_CHECK_ARG(img_w > 0.0f && img_h > 0.0f, "ym_decode_nms_strided_wh: img_w %g, img_h %g must be > 0",
+                 double(img_w), double(img_h));
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_w, img_h, false, 0,
                            workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index, stream);
 }
 
@@ -840,8 +855,21 @@ extern "C" int ym_decode_nms_cls(const float* pred, int64_t B, int64_t N, int64_
                                  int max_det, void* workspace, size_t workspace_bytes, int32_t* out_count,
                                  float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index,
                                  void* stream) {
-    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, true, max_det,
-                           workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index, stream);
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_size, img_size, true,
+                           max_det, workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                           stream);
+}
+
+extern "C" int ym_decode_nms_cls_wh(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
+                                    int64_t img_stride, int64_t col_stride, float conf, float iou_thr, float img_w,
+                                    float img_h, int max_det, void* workspace, size_t workspace_bytes,
+                                    int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels,
+                                    int64_t* out_index, void* stream) {
+    YM_CHECK_ARG(img_w > 0.0f && img_h > 0.0f, "ym_decode_nms_cls_wh: img_w %g, img_h %g must be > 0", double(img_w),
+                 double(img_h));
+    return decode_nms_impl(pred, B, N, C, row_stride, img_stride, col_stride, conf, iou_thr, img_w, img_h, true,
+                           max_det, workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                           stream);
 }
 
 extern "C" int ym_decode_nms(const float* pred, int64_t B, int64_t N, int64_t C, int64_t row_stride,
@@ -870,7 +898,7 @@ static int nms_impl(const float* boxes, const float* scores, const int64_t* labe
     hipLaunchKernelGGL(direct_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st,
                        reinterpret_cast<const float4*>(boxes), scores, labels, n, w);
     YM_LAUNCH_CHECK("nms direct");
-    return launch_nms(1, n, iou_thr, 1.0f, 0, w, count, ob, os, ol, keep, st, cls, max_det, labels);
+    return launch_nms(1, n, iou_thr, 1.0f, 1.0f, 0, w, count, ob, os, ol, keep, st, cls, max_det, labels);
 }
 
 extern "C" int ym_nms(const float* boxes, const float* scores, int64_t n, float iou_thr, void* workspace,

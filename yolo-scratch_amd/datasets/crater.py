@@ -112,15 +112,19 @@ class CraterDatasetCUDA(torch.utils.data.Dataset):
         return img, boxes, labels, idx
 
 
-def pack_images(imgs, img_size: int, channels: int = 1, letterbox: bool = False):
+def pack_images(imgs, img_size: int, channels: int = 1, letterbox: bool = False, rect: bool = False):
     """Raw uint8 images -> one pinned byte buffer + meta (B, 3) int64 {offset, h, w}.  channels == 1: (1, h, w)
     images; channels > 1: pixel-interleaved (h, w, channels) images, as the decoder yields them (offsets count
     h * w * channels bytes), and the dict also carries "img_ch".  `letterbox`: the dict also carries "img_lb",
     (B, 4) int32 rows (nw, nh, left, top) of datasets.letterbox.letterbox_geometry, and prepare_batch letterboxes
-    the images instead of stretching them."""
+    the images instead of stretching them.  `rect` (with `letterbox`): the frame is datasets.letterbox.rect_frame of
+    these images instead of img_size x img_size; "img_lb" is the geometry in that frame and "img_frame" holds int32
+    (H, W)."""
     channels = int(channels)
     if not 1 <= channels <= 4:
         raise ValueError(f"pack_images: channels must be 1..4, got {channels}")
+    if rect and not letterbox:
+        raise ValueError("pack_images: rect=True needs letterbox=True (a rectangular frame keeps the aspect ratio)")
     if channels > 1:
         for t in imgs:
             if t.dim() != 3 or int(t.shape[-1]) != channels:
@@ -143,8 +147,11 @@ def pack_images(imgs, img_size: int, channels: int = 1, letterbox: bool = False)
     if channels > 1:
         out["img_ch"] = channels
     if letterbox:
-        from .letterbox import geometry_of
-        out["img_lb"] = torch.from_numpy(geometry_of(meta, int(img_size), int(img_size)))
+        from .letterbox import geometry_of, rect_frame
+        H, W = rect_frame(hw, int(img_size)) if rect else (int(img_size), int(img_size))
+        out["img_lb"] = torch.from_numpy(geometry_of(meta, H, W))
+        if rect:
+            out["img_frame"] = torch.tensor([H, W], dtype=torch.int32)
     return out
 
 
@@ -190,7 +197,10 @@ def prepare_batch(batch: dict, device) -> dict:
             tb = tb.pin_memory()
         out.pop("img_lb")
         S = out.pop("img_size")
-        out["img"] = letterbox_batch(out.pop("img_u8"), out.pop("img_meta"), tb.to(device, non_blocking=True), S, S,
+        # a rect batch (collate_fn_cuda(rect=True)) brings its own frame; read from the host copy, no sync
+        H, W = (int(v) for v in batch["img_frame"].tolist()) if "img_frame" in out else (S, S)
+        out.pop("img_frame", None)
+        out["img"] = letterbox_batch(out.pop("img_u8"), out.pop("img_meta"), tb.to(device, non_blocking=True), H, W,
                                      out.pop("img_ch", 1))
     elif "img_u8" in out:
         out["img"] = resize_batch(out.pop("img_u8"), out.pop("img_meta"), out.pop("img_size"), out.pop("img_ch", 1))

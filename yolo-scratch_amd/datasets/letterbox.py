@@ -8,6 +8,7 @@ derive nothing, so host and device cannot disagree about a size or an offset.
   map_labels        normalised source boxes -> normalised boxes of the letterboxed frame (what the loss and the
                     validation metrics see: ground truth and predictions agree there)
   unletterbox       ym_unletterbox_boxes: detections of the letterboxed frame -> source-pixel boxes
+  rect_frame        the minimal stride-multiple H x W frame of a batch (rectangular inference)
 """
 from __future__ import annotations
 
@@ -33,6 +34,28 @@ def letterbox_geometry(h0: int, w0: int, H: int, W: int, scaleup: bool = True):
     nw = min(W, max(1, math.floor(w0 * r + 0.5)))
     nh = min(H, max(1, math.floor(h0 * r + 0.5)))
     return nw, nh, (W - nw) // 2, (H - nh) // 2
+
+
+def rect_frame(hws, imgsz: int, stride: int = 32):
+    """(H, W) of the smallest frame with sides that are multiples of `stride` holding every (h0, w0) of `hws`
+    resized so that its longer side is `imgsz` (rectangular inference), in fp64: per image
+    r = imgsz / max(h0, w0), nh = min(imgsz, max(1, floor(h0 r + 0.5))), nw likewise; H = ceil(max nh / stride)
+    * stride, W likewise.  Images without pixels are ignored; none at all gives (stride, stride).  The image's place
+    in the frame is then letterbox_geometry(h0, w0, H, W)."""
+    imgsz, stride = int(imgsz), int(stride)
+    if stride < 1 or imgsz < stride or imgsz % stride:
+        raise ValueError(f"rect_frame: imgsz {imgsz} is not a positive multiple of the stride {stride}")
+    mh = mw = 0
+    for h0, w0 in hws:
+        h0, w0 = int(h0), int(w0)
+        if h0 <= 0 or w0 <= 0:
+            continue
+        r = imgsz / max(h0, w0)
+        mh = max(mh, min(imgsz, max(1, math.floor(h0 * r + 0.5))))
+        mw = max(mw, min(imgsz, max(1, math.floor(w0 * r + 0.5))))
+    if mh == 0:
+        return stride, stride
+    return -(-mh // stride) * stride, -(-mw // stride) * stride
 
 
 def _hw(meta):

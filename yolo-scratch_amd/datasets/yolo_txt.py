@@ -66,7 +66,7 @@ class YoloTxtDataset(torch.utils.data.Dataset):
         self.samples = [{"img_path": str(p),
                          "label_path": str((self.root / "labels" / p.relative_to(img_dir)).with_suffix(".txt"))}
                         for p in files]
-        self._cache = {}
+        self._cache, self._hw = {}, {}
         print(f"Loaded {len(self.samples)} image paths")
 
     def __len__(self):
@@ -90,6 +90,18 @@ class YoloTxtDataset(torch.utils.data.Dataset):
             if self.cache_images:
                 self._cache[i] = im
         return im
+
+    def image_hw(self, i: int):
+        """(h0, w0) of image i from the file's header, without decoding it; cached."""
+        if i < 0 or i >= len(self.samples):
+            raise IndexError(f"Index {i} out of range for dataset of size {len(self.samples)}")
+        hw = self._hw.get(i)
+        if hw is None:
+            from PIL import Image
+            with Image.open(self.samples[i]["img_path"]) as f:
+                w0, h0 = f.size
+            hw = self._hw[i] = (int(h0), int(w0))
+        return hw
 
     def __getitem__(self, idx):
         im = self.load_image(idx)

@@ -1,6 +1,7 @@
 """Run a trained YOLOv11 on image files (MI355X): boxes in each image's own pixels.
 
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --scale s --ch 3 --nc 80 --ema
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source video_frames/ --ch 3 --nc 80 --rect
 
 Per image `<save-dir>/<stem>.txt` with rows `cls cx cy w h conf` normalised to the source image (the label format of
 datasets/yolo_txt.py plus the confidence), and one `<save-dir>/predictions.json` with the pixel boxes.  The images
@@ -38,6 +39,9 @@ def build_parser():
     ap.add_argument("--iou", type=float, default=0.45)
     ap.add_argument("--max-det", type=int, default=300, help="boxes kept per image (0: no cap)")
     ap.add_argument("--ema", action="store_true", help="load the averaged weights (ema_state_dict) when present")
+    ap.add_argument("--rect", action="store_true",
+                    help="run each image in its minimal multiple-of-32 frame instead of the --imgsz square (--imgsz "
+                         "must be a multiple of 32); the files are walked by aspect ratio so batches share a frame")
     ap.add_argument("--save-dir", type=str, default="runs/predict")
     return ap
 
@@ -61,6 +65,14 @@ def read_image(path, ch):
         return np.array(f.convert({3: "RGB", 4: "RGBA"}[ch]), dtype=np.uint8)
 
 
+def header_ratio(path):
+    """h0 / w0 from the file's header, without decoding the image."""
+    from PIL import Image
+    with Image.open(path) as f:
+        w0, h0 = f.size
+    return h0 / max(w0, 1)
+
+
 def txt_rows(det, h0, w0):
     """`cls cx cy w h conf` rows, normalised to the h0 x w0 source image."""
     rows = []
@@ -82,19 +94,23 @@ def main(argv=None):
     key = T.load_checkpoint(args.weights, model, device, ema=args.ema)
     print(f"Loaded {key} from {args.weights}")
     predictor = Predictor(model, imgsz=args.imgsz, ch=args.ch, conf=args.conf, iou=args.iou, max_det=args.max_det,
-                          class_aware=True, device=device, batch=args.batch)
+                          class_aware=True, device=device, batch=args.batch, rect=args.rect)
     save_dir = Path(args.save_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
-    results = []
-    for lo in range(0, len(files), args.batch):
-        chunk = files[lo:lo + args.batch]
-        images = [read_image(f, args.ch) for f in chunk]
-        for f, im, det in zip(chunk, images, predictor(images)):
+    order = list(range(len(files)))
+    if args.rect:
+        order.sort(key=lambda i: header_ratio(files[i]))             # stable: neighbours share a frame
+    results = [None] * len(files)
+    for lo in range(0, len(order), args.batch):
+        chunk = order[lo:lo + args.batch]
+        images = [read_image(files[i], args.ch) for i in chunk]
+        for i, im, det in zip(chunk, images, predictor(images)):
+            f = files[i]
             det = {k: v.cpu() for k, v in det.items()}
             h0, w0 = im.shape[:2]
             (save_dir / f"{f.stem}.txt").write_text("".join(r + "\n" for r in txt_rows(det, h0, w0)))
-            results.append({"image": str(f), "height": h0, "width": w0, "boxes": det["boxes"].tolist(),
-                            "scores": det["scores"].tolist(), "labels": det["labels"].tolist()})
+            results[i] = {"image": str(f), "height": h0, "width": w0, "boxes": det["boxes"].tolist(),
+                          "scores": det["scores"].tolist(), "labels": det["labels"].tolist()}
     (save_dir / "predictions.json").write_text(json.dumps({"weights": str(args.weights), "state": key,
                                                            "imgsz": args.imgsz, "conf": args.conf, "iou": args.iou,
                                                            "images": results}))

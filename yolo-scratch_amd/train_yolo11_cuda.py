@@ -91,7 +91,7 @@ def _head_nc(model):
 
 @torch.no_grad()
 def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_threshold=0.45, max_batches=None,
-             dp=None, per_class=False, nc=None, nms_per_class=False, max_det=0):
+             dp=None, per_class=False, nc=None, nms_per_class=False, max_det=0, max_frames=None):
     """Validation + metrics (reference :101-262).  Under data parallelism (`dp`, a GradSync) each
     rank evaluates its ValShard of the val set (decode + NMS on its own GPU), the per-image
     detections are gathered to rank 0 in the global image order and evaluate_detections runs there
@@ -105,7 +105,12 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
 
     `nms_per_class` (needs `per_class`: only that read has classes for labels): class-aware NMS, a box is
     suppressed by kept boxes of its own class only, and at most `max_det` boxes per image (0: no cap), the
-    usual YOLO evaluation recipe.  The result's keys do not change."""
+    usual YOLO evaluation recipe.  The result's keys do not change.
+
+    A batch whose image is not square (the `--val-rect` loader) is decoded with its own (H, W); the
+    metrics stay in the frame's normalised coordinates, where GT and predictions agree.  `max_frames`: keep the
+    eval plans of at most that many most-recently-used (B, H, W) frames (yolomi.graph.FrameLRU); None, the
+    default, never drops a plan."""
     if nms_per_class and not per_class:
         raise ValueError("validate(nms_per_class=True) needs per_class=True: the reference's literal read of the "
                          "eval output has anchor indices for labels, and suppression by those means nothing")
@@ -114,11 +119,17 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
     model.eval()
     if per_class and nc is None:
         nc = _head_nc(model)
+    lru = None
+    if max_frames is not None:
+        from yolomi.graph import FrameLRU
+        lru = FrameLRU.of(model, max_frames)
     sums = torch.zeros(4, device=device)
     all_predictions, all_targets = [], []
     batches = 0
     for batch in _tqdm(dataloader, desc="Validating"):
         batch = prepare_batch(batch, device)
+        if lru is not None:
+            lru.touch(batch["img"].shape[0], batch["img"].shape[-2], batch["img"].shape[-1])
         preds = model(batch["img"])
         loss, loss_items = criterion(preds, batch)
         sums[0] += loss
@@ -128,12 +139,14 @@ def validate(model, dataloader, criterion, device, conf_threshold=0.25, iou_thre
             # labels must be classes: decode the anchor-major view (B, A, 4+nc) of the eval output, read in place.
             # The reference's literal read of (B, 4+nc, A) takes anchors for classes
             decoded = decoded.transpose(1, 2)
+        # a rectangular frame (a --val-rect batch) is normalised per axis; a square one makes the call it always made
+        fh, fw = int(batch["img"].shape[-2]), int(batch["img"].shape[-1])
+        frame = fw if fh == fw else (fh, fw)
         if nms_per_class:
-            predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold,
-                                                         iou_threshold, device, class_aware=True, max_det=max_det)
+            predictions = decode_predictions_for_metrics(decoded, frame, conf_threshold, iou_threshold, device,
+                                                         class_aware=True, max_det=max_det)
         else:
-            predictions = decode_predictions_for_metrics(decoded, batch["img"].shape[-1], conf_threshold,
-                                                         iou_threshold, device)
+            predictions = decode_predictions_for_metrics(decoded, frame, conf_threshold, iou_threshold, device)
         all_predictions.extend(predictions)
         bidx, bboxes, cls = batch["batch_idx"], batch["bboxes"], batch["cls"]
         for i in range(batch["img"].shape[0]):
@@ -285,14 +298,17 @@ def resume_checkpoint(path, model, optimizer, device, ema=None):
     return ckpt["epoch"] + 1, ckpt.get("best_loss", float("inf")), ckpt.get("best_mAP50", 0.0)
 
 
-def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None, channels=1, letterbox=False):
+def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate=None, channels=1, letterbox=False,
+                 val_rect=False):
     """The reference's split and loaders (:491-543): seed-42 permutation, Subset train / val,
     shuffled train loader, ordered val loader, drop_last=False.  Under data parallelism the train set
     is sharded by a DistributedSampler(shuffle=True, drop_last=True): every rank gets the same number
     of samples and so the same number of batches (a rank with one batch more would enter the gradient
     all-reduce alone and hang), reshuffled every epoch (set_epoch); the val set by ValShard (no
     padding: no image counted twice).  `channels`: the dataset's image planes, handed to the collate; `letterbox`:
-    both loaders keep the images' aspect ratio (datasets/letterbox.py) instead of stretching them.
+    both loaders keep the images' aspect ratio (datasets/letterbox.py) instead of stretching them.  `val_rect`: the
+    val loader alone letterboxes into each batch's minimal stride-multiple frame (collate rect=True) and walks its
+    images (its shard, under data parallelism) by aspect ratio (datasets.RectSampler), so neighbours share a frame.
     -> (train_loader, val_loader, train_sampler or None)."""
     import functools
     from torch.utils.data import DataLoader, DistributedSampler, Subset
@@ -309,9 +325,37 @@ def make_loaders(dataset, val_split, batch, workers, imgsz, dp_ctx=None, collate
         from yolomi.dist import ValShard
         sampler = DistributedSampler(tr, num_replicas=dp_ctx.world, rank=dp_ctx.rank, shuffle=True, seed=0,
                                      drop_last=True)
-        return (DataLoader(tr, sampler=sampler, **kw),
-                DataLoader(va, sampler=ValShard(len(va), dp_ctx.rank, dp_ctx.world), **kw), sampler)
+        vs = ValShard(len(va), dp_ctx.rank, dp_ctx.world)
+        val = rect_val_loader(va, vs, batch, imgsz, channels, **kw) if val_rect else DataLoader(va, sampler=vs, **kw)
+        return DataLoader(tr, sampler=sampler, **kw), val, sampler
+    if val_rect:
+        return (DataLoader(tr, shuffle=True, **kw),
+                rect_val_loader(va, range(len(va)), batch, imgsz, channels, **kw), None)
     return DataLoader(tr, shuffle=True, **kw), DataLoader(va, shuffle=False, **kw), None
+
+
+def rect_val_loader(va, inner, batch, imgsz, channels=1, **kw):
+    """The --val-rect loader over the Subset `va`: the indices of `inner` (range(len(va)), or a rank's ValShard)
+    walked by aspect ratio, every batch letterboxed into its own minimal stride-multiple frame.  `kw`: further
+    DataLoader arguments."""
+    import functools
+    from torch.utils.data import DataLoader
+    col = functools.partial(collate_fn, img_size=imgsz, channels=channels, letterbox=True, rect=True)
+    return DataLoader(va, sampler=_rect_sampler(va, inner), **dict(kw, batch_size=batch, collate_fn=col))
+
+
+def _rect_sampler(subset, inner):
+    """`inner` (indices into the val Subset) ordered by the images' h0 / w0 when the dataset can tell the sizes
+    without decoding (image_hw); otherwise as it is: the per-batch frame still applies."""
+    from datasets import RectSampler
+    ds = subset.dataset
+    if not hasattr(ds, "image_hw"):
+        return inner
+    ratios = []
+    for i in subset.indices:
+        h0, w0 = ds.image_hw(i)
+        ratios.append(h0 / max(w0, 1))
+    return RectSampler(inner, ratios)
 
 
 class _SyntheticLoader:
@@ -345,6 +389,10 @@ class _Parser(argparse.ArgumentParser):
             self.error("--data-format yolo decodes to 1 (luma), 3 (RGB) or 4 (RGBA) planes")
         if ns.letterbox and ns.synthetic:
             self.error("--letterbox acts on a dataset's images: synthetic batches are generated at --imgsz")
+        if ns.val_rect and ns.synthetic:
+            self.error("--val-rect acts on a dataset's images: synthetic batches are generated at --imgsz")
+        if ns.val_rect and ns.imgsz % 32:
+            self.error("--val-rect needs --imgsz to be a multiple of the 32-pixel stride")
         if not 1 <= ns.ch <= 4 or ns.nc < 1:
             self.error("--ch is 1..4 and --nc at least 1")
         return ns, rest
@@ -417,6 +465,10 @@ def build_parser():
     ap.add_argument("--letterbox", action="store_true",
                     help="keep the images' aspect ratio in the train and val loaders (resize + centred pad on the GPU, "
                          "datasets/letterbox.py) instead of stretching them to --imgsz; metrics stay in that frame")
+    ap.add_argument("--val-rect", action="store_true",
+                    help="validate on rectangular frames: each val batch is letterboxed into its own minimal "
+                         "multiple-of-32 frame and the val set is walked by aspect ratio (DESIGN §23); the train "
+                         "loader is unchanged")
     return ap
 
 
@@ -449,7 +501,7 @@ def main():
             dataset = CraterDatasetCUDA(args.data, img_size=args.imgsz, cache_images=False, augment=True)
         train_loader, val_loader, train_sampler = make_loaders(dataset, args.val_split, args.batch, args.workers,
                                                                args.imgsz, dp_ctx, channels=args.ch,
-                                                               letterbox=args.letterbox)
+                                                               letterbox=args.letterbox, val_rect=args.val_rect)
 
     model = build_model(args.cfg, args.scale, args.ch, args.nc, device)
     if rank0:
@@ -505,7 +557,8 @@ def main():
         # with --ema the averaged weights are the ones validated (and so the ones best.pt is selected by)
         vm = validate(ema.refresh() if ema is not None else model, val_loader, criterion, device,
                       conf_threshold=args.val_conf, iou_threshold=0.45, max_batches=args.max_val_batches, dp=dp,
-                      per_class=args.val_per_class, nms_per_class=args.val_nms_per_class, max_det=args.val_max_det)
+                      per_class=args.val_per_class, nms_per_class=args.val_nms_per_class, max_det=args.val_max_det,
+                      max_frames=8 if args.val_rect else None)
         if not rank0:
             continue
         print(f"\nEpoch {epoch + 1}/{args.epochs} | LR: {lr:.6f}")

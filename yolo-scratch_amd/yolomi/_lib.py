@@ -90,6 +90,8 @@ SIGNATURES = {
     "ym_nms_workspace_size": (SZ, [I64, I64]),
     "ym_decode_nms": (R, [P, I64, I64, I64, I64, I64, F32, F32, F32, P, SZ, P, P, P, P, P, P]),
     "ym_decode_nms_strided": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, P, SZ, P, P, P, P, P, P]),
+    "ym_decode_nms_strided_wh": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, F32, P, SZ, P, P, P, P, P, P]),
+    "ym_decode_nms_cls_wh": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, F32, INT, P, SZ, P, P, P, P, P, P]),
     "ym_nms": (R, [P, P, I64, F32, P, SZ, P, P, P]),
     "ym_nms_cls_workspace_size": (SZ, [I64, I64]),
     "ym_decode_nms_cls": (R, [P, I64, I64, I64, I64, I64, I64, F32, F32, F32, INT, P, SZ, P, P, P, P, P, P]),

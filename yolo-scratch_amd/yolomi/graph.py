@@ -1646,3 +1646,53 @@ def run_model(model, img: torch.Tensor):
         # a fresh tensor: the plan's buffer is rewritten by the next forward of this shape
         head = plan.head.clone()
     return head, plan
+
+
+def drop_eval_plans(model, B: int, H: int, W: int) -> int:
+    """Forget the whole-model eval plans of input shape (B, *, H, W): their activations and captured graph go back
+    to the allocator.  For callers that walk many frames (rectangular inference), where run_model's
+    cache would otherwise keep one plan per frame.  The device is synchronised first, so no launch still reads
+    a buffer that is freed.  Training plans are under another key and are never touched; an eval plan that is
+    pending is kept.  Returns the number of plans dropped."""
+    cache = model.__dict__.get("_ym_plans")
+    key = ("model", int(B), int(H), int(W), False)
+    pool = cache.get(key) if cache else None
+    if not pool:
+        return 0
+    torch.cuda.synchronize(pool[0].dev)          # the plan's scheduler streams and the caller's stream
+    keep = [p for p in pool if p.pending]
+    n = len(pool) - len(keep)
+    if keep:
+        cache[key] = keep
+    else:
+        del cache[key]
+    return n
+
+
+class FrameLRU:
+    """At most `max_frames` most-recently-used (B, H, W) eval frames of one model: touch() before a forward at
+    that frame drops the plans of the frames that fall out.  FrameLRU.of(model, n) is the model's own list, so
+    every caller that bounds this model's frames (a Predictor, each epoch's validation) shares one history."""
+
+    @classmethod
+    def of(cls, model, max_frames: int = 8):
+        lru = model.__dict__.get("_ym_frame_lru")
+        if lru is None:
+            lru = model.__dict__["_ym_frame_lru"] = cls(model, max_frames)
+        elif int(max_frames) < 1:
+            raise ValueError("FrameLRU: max_frames is at least 1")
+        lru.max_frames = int(max_frames)
+        return lru
+
+    def __init__(self, model, max_frames: int = 8):
+        if int(max_frames) < 1:
+            raise ValueError("FrameLRU: max_frames is at least 1")
+        self.model, self.max_frames, self.frames = model, int(max_frames), []
+
+    def touch(self, B: int, H: int, W: int):
+        key = (int(B), int(H), int(W))
+        if key in self.frames:
+            self.frames.remove(key)
+        self.frames.append(key)
+        while len(self.frames) > self.max_frames:
+            drop_eval_plans(self.model, *self.frames.pop(0))

@@ -60,6 +60,9 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
     many boxes per image, the best-scoring kept ones (ym_decode_nms_cls).  With the defaults: the
     reference's class-agnostic NMS (ym_decode_nms_strided).
 
+    `img_size`: a number, the side of a square frame (ym_decode_nms_strided / ym_decode_nms_cls), or `(img_h, img_w)`,
+    a frame of img_h rows and img_w columns: kept boxes are x / img_w, y / img_h (the _wh entry points).
+
     `padded`: one dict for the batch instead of the list: boxes (B, N, 4), scores / labels (B, N), "count" the
     per-image counts on the device (int32) and "counts" the same on the host; rows past an image's count are
     unspecified (what datasets.letterbox.unletterbox takes)."""
@@ -71,6 +74,11 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
     B, N, W = p.shape
     C = W - 4
     dev = p.device
+    wh = None
+    if isinstance(img_size, (tuple, list, torch.Size)):
+        if len(img_size) != 2:
+            raise ValueError(f"decode_nms: img_size is a number or (img_h, img_w), got {tuple(img_size)}")
+        wh = (float(img_size[1]), float(img_size[0]))
     if max_det and not class_aware:
         raise ValueError("decode_nms: max_det needs class_aware=True (the class-agnostic path has no cap)")
     ws_bytes = (lib().ym_nms_cls_workspace_size if class_aware else lib().ym_nms_workspace_size)(B, max(N, 1))
@@ -81,7 +89,15 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
     labels = torch.empty(B, N, dtype=torch.int64, device=dev)
     index = torch.empty(B, N, dtype=torch.int64, device=dev)
     # a row's elements may be strided (the anchor-major view y.transpose(1, 2) of the eval output): read in place
-    if class_aware:
+    if wh is not None and class_aware:
+        call("ym_decode_nms_cls_wh", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf),
+             float(iou_thr), wh[0], wh[1], int(max_det), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores),
+             ptr(labels), ptr(index), stream_ptr(dev))
+    elif wh is not None:
+        call("ym_decode_nms_strided_wh", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf),
+             float(iou_thr), wh[0], wh[1], ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores), ptr(labels),
+             ptr(index), stream_ptr(dev))
+    elif class_aware:
         call("ym_decode_nms_cls", ptr(p), B, N, C, p.stride(1), p.stride(0), p.stride(2), float(conf),
              float(iou_thr), float(img_size), int(max_det), ptr(ws), ws_bytes, ptr(cnt), ptr(boxes), ptr(scores),
              ptr(labels), ptr(index), stream_ptr(dev))

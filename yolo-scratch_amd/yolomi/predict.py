@@ -7,6 +7,10 @@ Predictor chains four device steps per batch, none of which leaves the GPU:
   decode + NMS               yolomi.post.decode_nms on the anchor-major view (labels are classes)
   ym_unletterbox_boxes       kept boxes -> source-pixel xyxy through the same geometry table
 The host synchronises once per batch, for the per-image counts.
+
+`rect=True`: every image gets its own minimal multiple-of-32 frame (datasets.letterbox.rect_frame) in
+place of the imgsz x imgsz square, images are grouped by frame, and the four steps run per group at (H, W); the
+results come back in input order.
 """
 from __future__ import annotations
 
@@ -21,10 +25,14 @@ class Predictor:
     """predictor(images) -> per image {"boxes" (n, 4) fp32 xyxy in source pixels, "scores" (n,), "labels" (n,)}, on
     the device.  `images`: uint8 arrays (or tensors), (h, w, ch) — (h, w) also for one plane.  `class_aware`: NMS
     within a class, at most `max_det` boxes per image (0: no cap); without it the class-agnostic NMS, which has no
-    cap.  `batch`: the fixed batch size of the forward; more images run in several batches."""
+    cap.  `batch`: the fixed batch size of the forward; more images run in several batches.  `rect`: rectangular
+    frames, one per image shape (imgsz must be a multiple of 32); images of one frame run together in chunks of
+    `batch`, so the plan and graph of (batch, H, W) replay, and the eval plans of at most `max_frames`
+    most-recently-used frames are kept (yolomi.graph.FrameLRU).  Without `rect` nothing is ever dropped."""
 
     def __init__(self, model, imgsz: int = 640, ch: int | None = None, conf: float = 0.25, iou: float = 0.45,
-                 max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114):
+                 max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114,
+                 rect: bool = False, max_frames: int = 8):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise YolomiError("Predictor runs on the MI355X only (no CPU fallback)")
@@ -37,6 +45,12 @@ class Predictor:
         self.max_det, self.class_aware, self.batch, self.fill = int(max_det), bool(class_aware), int(batch), int(fill)
         if self.batch < 1 or self.imgsz < 1:
             raise ValueError("Predictor: batch and imgsz are at least 1")
+        self.rect, self._lru = bool(rect), None
+        if self.rect:
+            from datasets.letterbox import rect_frame
+            from .graph import FrameLRU
+            rect_frame([], self.imgsz)                               # raises unless imgsz is a multiple of the stride
+            self._lru = FrameLRU.of(self.model, max_frames)
 
     def _raw(self, im) -> torch.Tensor:
         """One image in the layout pack_images takes: (1, h, w) for one plane, (h, w, ch) otherwise."""
@@ -52,32 +66,54 @@ class Predictor:
         raise ValueError(f"Predictor: expected (h, w{', ' + str(self.ch) if self.ch > 1 else ''}) uint8 images, got "
                          f"{tuple(t.shape)}")
 
-    def letterbox(self, images):
-        """pack + ym_letterbox_u8c of up to `batch` images, padded with empty ones -> (img (batch, ch, S, S) on the
-        device, the device table of ym_lb_entry)."""
+    def letterbox(self, images, frame=None):
+        """pack + ym_letterbox_u8c of up to `batch` images, padded with empty ones -> (img (batch, ch, H, W) on the
+        device, the device table of ym_lb_entry).  `frame`: (H, W); None: the imgsz x imgsz square."""
         from datasets.crater import pack_images
         from datasets.letterbox import lb_table, letterbox_batch, table_bytes
         raw = [self._raw(im) for im in images]
         empty = torch.empty((1, 0, 0) if self.ch == 1 else (0, 0, self.ch), dtype=torch.uint8)
         raw += [empty] * (self.batch - len(raw))
         packed = pack_images(raw, self.imgsz, self.ch)
-        S = self.imgsz
-        tb = table_bytes(lb_table(packed["img_meta"], S, S), self.batch).pin_memory()
+        H, W = frame or (self.imgsz, self.imgsz)
+        tb = table_bytes(lb_table(packed["img_meta"], H, W), self.batch).pin_memory()
         mv = lambda t: t.to(self.device, non_blocking=True)          # noqa: E731
         table = mv(tb)
-        return letterbox_batch(mv(packed["img_u8"]), mv(packed["img_meta"]), table, S, S, self.ch, self.fill), table
+        return letterbox_batch(mv(packed["img_u8"]), mv(packed["img_meta"]), table, H, W, self.ch, self.fill), table
 
     @torch.no_grad()
-    def _run(self, images):
+    def _run(self, images, frame=None):
         from datasets.letterbox import unletterbox
-        img, table = self.letterbox(images)
+        img, table = self.letterbox(images, frame)
+        H, W = frame or (self.imgsz, self.imgsz)
+        if self._lru is not None:
+            self._lru.touch(self.batch, H, W)
         y = self.model(img)[0]                                       # (batch, 4 + nc, A)
-        dets = _post.decode_nms(y.transpose(1, 2), self.imgsz, self.conf, self.iou, class_aware=self.class_aware,
-                                max_det=self.max_det if self.class_aware else 0, padded=True)
-        return unletterbox(dets, table, self.imgsz, self.imgsz)[:len(images)]
+        dets = _post.decode_nms(y.transpose(1, 2), self.imgsz if frame is None else (H, W), self.conf, self.iou,
+                                class_aware=self.class_aware, max_det=self.max_det if self.class_aware else 0,
+                                padded=True)
+        return unletterbox(dets, table, H, W)[:len(images)]
+
+    def frame_of(self, im):
+        """(H, W) of one image's rectangular frame."""
+        from datasets.letterbox import rect_frame
+        t = self._raw(im)
+        hw = (int(t.shape[-2]), int(t.shape[-1])) if self.ch == 1 else (int(t.shape[0]), int(t.shape[1]))
+        return rect_frame([hw], self.imgsz)
 
     def __call__(self, images):
         images = list(images)
+        if self.rect:
+            groups = {}                                              # frame -> input positions, first seen first
+            for i, im in enumerate(images):
+                groups.setdefault(self.frame_of(im), []).append(i)
+            out = [None] * len(images)
+            for frame, pos in groups.items():
+                for lo in range(0, len(pos), self.batch):
+                    chunk = pos[lo:lo + self.batch]
+                    for i, d in zip(chunk, self._run([images[i] for i in chunk], frame)):
+                        out[i] = d
+            return out
         out = []
         for lo in range(0, len(images), self.batch):
             out += self._run(images[lo:lo + self.batch])
