@@ -581,6 +581,50 @@ int ym_letterbox_u8c(const uint8_t* src, const int64_t* meta, const ym_lb_entry*
 int ym_unletterbox_boxes(const float* boxes, const int32_t* count, const ym_lb_entry* table_dev, int64_t B, int64_t N,
                          int out_h, int out_w, float* out, void* stream);
 
+/* Sliced inference: the network runs on overlapping full-resolution windows ("tiles") of sources that
+ * were uploaded once, and the tiles' candidates are merged in source pixels by one NMS per source image.  The host
+ * plans the windows in integers (datasets/slicing.py) and hands them over in this table, one entry per tile; the
+ * geometry of a window in its frame is letterbox_geometry(th, tw, out_h, out_w), unchanged. */
+typedef struct ym_tile_entry {
+    int32_t src;               /* image index into meta; outside [0, n_images): an all-fill tile, no candidates */
+    int32_t x0, y0, tw, th;    /* the window in source pixels */
+    int32_t nw, nh, left, top; /* the window resized to nw x nh, first pixel at (left, top) of the frame */
+    int32_t edges;             /* bit 0 left, 1 right, 2 top, 3 bottom: that window side is interior */
+    float sx, sy;              /* frame pixels -> window pixels */
+} ym_tile_entry;               /* 48 bytes */
+/* src / meta as for ym_letterbox_u8c; out planar (n_tiles, ch, out_h, out_w) fp32.  Tile t is, bit for bit, what
+ * ym_letterbox_u8c writes for a stand-alone image holding exactly the window's pixels with the entry {nw, nh, left,
+ * top, w0 = tw, h0 = th}: the resize taps clamp at the window's last row and column, not at the image's, and
+ * (nw, nh) == (tw, th) is a copy.  A tile whose src is out of range, whose tw, th, nw or nh is <= 0, or whose window
+ * does not lie inside the image as `meta` gives it, is all fill and reads no source byte. */
+int ym_slice_letterbox_u8c(const uint8_t* src, const int64_t* meta, int n_images, const ym_tile_entry* table_dev,
+                           int n_tiles, int ch, int out_h, int out_w, int fill, float* out, void* stream);
+/* Decode + NMS over tiles.  pred is read as (T, N, 4 + C): element (t, n, c) at pred[t * tile_stride + n * row_stride
+ * + c * col_stride]; image g owns the tiles [tile_begin[g], tile_begin[g + 1]) (tile_begin: HOST array of G + 1
+ * values) and its rows are their rows in (tile, row) order.  R = N * (the largest tile count of an image) is the
+ * capacity of every output per image: out_count (G), out_boxes (G, R, 4), out_scores / out_labels / out_index /
+ * out_row (G, R).
+ *   candidate   ym_decode_nms_strided's rule: max class score > conf, the first maximal class, xywh -> xyxy in
+ *               frame pixels
+ *   map         fp32, every step rounded: u = min(max((x - left) * sx, 0), tw), X = u + x0; v, Y likewise from top,
+ *               sy, th, y0
+ *   edge > 0    a candidate is dropped when (edges & 1) && u1 < edge, (edges & 2) && u2 > tw - edge,
+ *               (edges & 4) && v1 < edge or (edges & 8) && v2 > th - edge: a tile border cuts it, and the overlap
+ *               lets a neighbouring tile see it whole
+ * Dropped rows, rows of tiles with src < 0 and the padding rows of images with fewer tiles are no candidates.  The
+ * mapped boxes are then suppressed per image as ym_decode_nms_strided does (class_aware: as ym_decode_nms_cls, with
+ * max_det), in the order score descending, filtered index ascending.  out_boxes: source-pixel xyxy, unnormalised;
+ * out_index: the filtered index; out_row (may be NULL): the row in the image's concatenation, tile = row / N.
+ * YM_ERR_ARG before any launch: G < 0, tile_begin not monotone from >= 0 or tile_begin[G] > T, R >= 2^30, a NaN
+ * edge, max_det < 0, max_det > 0 without class_aware.  Workspace: ym_decode_nms_tiles_workspace_size (callable
+ * without a GPU). */
+size_t ym_decode_nms_tiles_workspace_size(int64_t G, int64_t R, int class_aware);
+int ym_decode_nms_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride, int64_t tile_stride,
+                        int64_t col_stride, const ym_tile_entry* table_dev, const int64_t* tile_begin, int64_t G,
+                        float conf, float iou_thr, float edge, int class_aware, int max_det, void* workspace,
+                        size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
+                        int64_t* out_labels, int64_t* out_index, int64_t* out_row, void* stream);
+
 /* ------------------------------------------------------------------ optimizer tail
  * clip_grad_norm_(params, max_norm) + AdamW.step() over every parameter (train_yolo11_cuda.py:58-62,
  * 440-451).  The parameters form one flat index space: entry e covers elements [offset, offset + n)

@@ -33,6 +33,7 @@
 
 static_assert(sizeof(ym_aug_tile) == 88 && sizeof(ym_aug_entry) == 432, "ym_aug_entry layout (yolomi/_lib.py)");
 static_assert(sizeof(ym_lb_entry) == 32, "ym_lb_entry layout (yolomi/_lib.py)");
+static_assert(sizeof(ym_tile_entry) == 48, "ym_tile_entry layout (yolomi/_lib.py)");
 
 /* OpenCV resizeGeneric_ coefficients of output index d (see csrc/preprocess.hip) */
 YM_HD static inline void ym_aug_lin_coeff(int d, double scale, int n, int& s, int& a0, int& a1) {
@@ -202,6 +203,50 @@ YM_HD static inline void ym_lb_sample_c(const uint8_t* src, const int64_t* meta,
     }
     ym_aug_taps t;
     ym_aug_lin_taps_wh(im, h0, w0, ch, e->nw, e->nh, int(u), int(w), t);
+    for (int c = 0; c < ch; ++c) v[c] = ym_aug_taps_value(t, c);
+}
+
+/* ---------------------------------------------------------------- tiles (ym_slice_letterbox_u8c)
+ * A tile is a tw x th window of a wider image: its rows lie `pitch` bytes apart, and everything else is the
+ * letterbox of a stand-alone tw x th image, so the second taps clamp at the window's last column and row. */
+
+/* ym_aug_set_taps for the th x tw window at `win` whose rows are `pitch` bytes apart */
+YM_HD static inline void ym_aug_set_taps_pitch(const uint8_t* win, int th, int tw, int ch, int64_t pitch, int sx,
+                                               int a0, int a1, int sy, int b0, int b1, ym_aug_taps& t) {
+    const int sx1 = sx + 1 < tw ? sx + 1 : tw - 1, sy1 = sy + 1 < th ? sy + 1 : th - 1;
+    t.r0 = win + int64_t(sy) * pitch;
+    t.r1 = win + int64_t(sy1) * pitch;
+    t.o0 = int64_t(sx) * ch;
+    t.o1 = int64_t(sx1) * ch;
+    t.a0 = a0, t.a1 = a1, t.b0 = b0, t.b1 = b1;
+}
+
+/* true: the entry names an image of `meta` and a window with pixels that lies inside it; false: the tile is fill */
+YM_HD static inline bool ym_tile_valid(const int64_t* meta, int n_images, const ym_tile_entry* e) {
+    if (e->src < 0 || e->src >= n_images || e->tw <= 0 || e->th <= 0 || e->nw <= 0 || e->nh <= 0) return false;
+    const int64_t h0 = meta[3 * int64_t(e->src) + 1], w0 = meta[3 * int64_t(e->src) + 2];
+    return e->x0 >= 0 && e->y0 >= 0 && int64_t(e->x0) + e->tw <= w0 && int64_t(e->y0) + e->th <= h0;
+}
+
+/* ym_slice_letterbox_u8c: the `ch` values v[0..ch) of frame pixel (x, y) of the tile `e` describes */
+YM_HD static inline void ym_tile_sample_c(const uint8_t* src, const int64_t* meta, int n_images, int ch,
+                                          const ym_tile_entry* e, int fill, int x, int y, int* v) {
+    const int64_t u = int64_t(x) - e->left, w = int64_t(y) - e->top;
+    if (!ym_tile_valid(meta, n_images, e) || u < 0 || u >= e->nw || w < 0 || w >= e->nh) {
+        for (int c = 0; c < ch; ++c) v[c] = fill & 255;
+        return;
+    }
+    const int64_t pitch = meta[3 * int64_t(e->src) + 2] * ch;
+    const uint8_t* win = src + meta[3 * int64_t(e->src)] + e->y0 * pitch + int64_t(e->x0) * ch;
+    if (e->nw == e->tw && e->nh == e->th) {
+        for (int c = 0; c < ch; ++c) v[c] = win[w * pitch + u * ch + c];
+        return;
+    }
+    int sx, a0, a1, sy, b0, b1;
+    ym_aug_lin_coeff(int(u), double(e->tw) / e->nw, e->tw, sx, a0, a1);
+    ym_aug_lin_coeff(int(w), double(e->th) / e->nh, e->th, sy, b0, b1);
+    ym_aug_taps t;
+    ym_aug_set_taps_pitch(win, e->th, e->tw, ch, pitch, sx, a0, a1, sy, b0, b1, t);
     for (int c = 0; c < ch; ++c) v[c] = ym_aug_taps_value(t, c);
 }
 

@@ -911,3 +911,190 @@ extern "C" int ym_nms_cls(const float* boxes, const float* scores, const int64_t
                           void* stream) {
     return nms_impl(boxes, scores, labels, n, iou_thr, true, max_det, workspace, workspace_bytes, keep, count, stream);
 }
+
+// ---------------------------------------------------------------- tiles (ym_decode_nms_tiles)
+// The candidate stage of sliced inference: the rowmax stage over every tile's rows, with the map to source pixels and
+// the tile-border filter fused into it (the box and the score are in registers there; a second launch would read and
+// write the 20-byte box / flag record of every row again and add a launch).  The rows of image g land in the image's
+// slice [g * R, (g + 1) * R) of the candidate arrays in (tile, row) order, so everything from nms_image_kernel
+// downward runs unchanged on (G, R) with clamp_norm = 0.  blockIdx.y walks the images of a launch, whose tile ranges
+// travel by value in the kernel arguments (TILE_SPAN images per launch): the host's tile_begin needs no copy of its
+// own, and the image's range is block-uniform.
+namespace ym {
+namespace {
+
+constexpr int TILE_SPAN = 32;
+struct TileSpan {
+    int32_t begin[TILE_SPAN + 1];
+};
+
+// the candidate arrays of launch_nms's image-kernel path alone (no bitmask path at clamp_norm = 0)
+inline size_t tiles_ws_bytes(int64_t G, int64_t R) {
+    const size_t n = size_t(G) * size_t(R);
+    return align256(n * 16) + 4 * align256(n * 4) + align256(size_t(G) * pow2_at_least(R) * 8) + 256;
+}
+
+inline Ws carve_tiles(void* base, int64_t G, int64_t R) {
+    char* p = static_cast<char*>(base);
+    const size_t n = size_t(G) * size_t(R);
+    Ws w;
+    w.box = reinterpret_cast<float4*>(p);    p += align256(n * sizeof(float4));
+    w.score = reinterpret_cast<float*>(p);   p += align256(n * sizeof(float));
+    w.label = reinterpret_cast<int32_t*>(p); p += align256(n * sizeof(int32_t));
+    w.flag = reinterpret_cast<int32_t*>(p);  p += align256(n * sizeof(int32_t));
+    w.frow = reinterpret_cast<int32_t*>(p);  p += align256(n * sizeof(int32_t));
+    w.keys = reinterpret_cast<uint64_t*>(p);
+    w.sbox = nullptr; w.mask = nullptr; w.kcount = nullptr; w.slabel = nullptr;
+    return w;
+}
+
+// row (x, y, bw, bh) of tile `e` with max score mx / label lab -> the candidate record at o: xywh -> xyxy in frame
+// pixels, then to source pixels in rounded fp32 steps; the flag also needs the box not to be cut by an interior side
+__device__ __forceinline__ void tile_candidate(const ym_tile_entry& e, float x, float y, float bw, float bh, float mx,
+                                               int lab, float conf, float edge, int64_t o, const Ws& w) {
+    const float hw = bw / 2.0f, hh = bh / 2.0f;
+    const float left = float(e.left), top = float(e.top), tw = float(e.tw), th = float(e.th);
+    const float u1 = fminf(fmaxf(__fmul_rn(__fsub_rn(x - hw, left), e.sx), 0.f), tw);
+    const float v1 = fminf(fmaxf(__fmul_rn(__fsub_rn(y - hh, top), e.sy), 0.f), th);
+    const float u2 = fminf(fmaxf(__fmul_rn(__fsub_rn(x + hw, left), e.sx), 0.f), tw);
+    const float v2 = fminf(fmaxf(__fmul_rn(__fsub_rn(y + hh, top), e.sy), 0.f), th);
+    bool cut = false;
+    if (edge > 0.0f)
+        cut = ((e.edges & 1) && u1 < edge) || ((e.edges & 2) && u2 > __fsub_rn(tw, edge)) ||
+              ((e.edges & 4) && v1 < edge) || ((e.edges & 8) && v2 > __fsub_rn(th, edge));
+    const float x0 = float(e.x0), y0 = float(e.y0);
+    w.box[o] = make_float4(__fadd_rn(u1, x0), __fadd_rn(v1, y0), __fadd_rn(u2, x0), __fadd_rn(v2, y0));
+    w.score[o] = mx;
+    w.label[o] = lab;
+    w.flag[o] = (mx > conf && !cut) ? 1 : 0;
+}
+
+// thread per row (C <= 64): rowmax_thread_kernel's scan; grid (ceil(R / 256), images of the launch)
+__global__ void rowmax_tiles_thread_kernel(const float* __restrict__ pred, int64_t N, int64_t C, int64_t rs,
+                                           int64_t ts, int64_t cs, const ym_tile_entry* __restrict__ table,
+                                           TileSpan span, int64_t g0, int64_t R, float conf, float edge, Ws w) {
+    const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j >= R) return;
+    const int64_t o = (g0 + blockIdx.y) * R + j;
+    const int64_t slot = j / N, n = j - slot * N;
+    const int64_t t = span.begin[blockIdx.y] + slot;
+    if (t >= span.begin[blockIdx.y + 1]) { w.flag[o] = 0; return; }     // padding row of an image with fewer tiles
+    const ym_tile_entry e = table[t];
+    if (e.src < 0) { w.flag[o] = 0; return; }
+    const float* r = pred + t * ts + n * rs;
+    float mx = r[4 * cs];
+    int lab = 0;
+    for (int64_t c = 1; c < C; ++c) {
+        float v = r[(4 + c) * cs];
+        if (v > mx) { mx = v; lab = int(c); }
+    }
+    tile_candidate(e, r[0], r[cs], r[2 * cs], r[3 * cs], mx, lab, conf, edge, o, w);
+}
+
+// wave per row (C > 64): rowmax_wave_kernel's scan; grid (ceil(R / 4), images of the launch)
+__global__ void rowmax_tiles_wave_kernel(const float* __restrict__ pred, int64_t N, int64_t C, int64_t rs, int64_t ts,
+                                         int64_t cs, const ym_tile_entry* __restrict__ table, TileSpan span,
+                                         int64_t g0, int64_t R, float conf, float edge, Ws w) {
+    const int64_t j = int64_t(blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64;
+    const int lane = threadIdx.x & 63;
+    if (j >= R) return;
+    const int64_t o = (g0 + blockIdx.y) * R + j;
+    const int64_t slot = j / N, n = j - slot * N;
+    const int64_t t = span.begin[blockIdx.y] + slot;
+    if (t >= span.begin[blockIdx.y + 1]) {
+        if (lane == 0) w.flag[o] = 0;
+        return;
+    }
+    const ym_tile_entry e = table[t];
+    if (e.src < 0) {
+        if (lane == 0) w.flag[o] = 0;
+        return;
+    }
+    const float* r = pred + t * ts + n * rs;
+    float mx = -INFINITY;
+    int64_t lab = INT64_MAX;
+    for (int64_t c = lane; c < C; c += 64) {
+        float v = r[(4 + c) * cs];
+        if (v > mx || (v == mx && c < lab)) { mx = v; lab = c; }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        float om = __shfl_xor(mx, s, 64);
+        int64_t ol = __shfl_xor(lab, s, 64);
+        if (om > mx || (om == mx && ol < lab)) { mx = om; lab = ol; }
+    }
+    if (lane == 0) tile_candidate(e, r[0], r[cs], r[2 * cs], r[3 * cs], mx, int(lab), conf, edge, o, w);
+}
+
+// kept filtered index -> row of the image's concatenation (frow survives the NMS kernel); grid (blocks, G)
+__global__ void tile_rows_kernel(int64_t R, Ws w, const int32_t* __restrict__ count,
+                                 const int64_t* __restrict__ index, int64_t* __restrict__ out_row) {
+    const int64_t base = int64_t(blockIdx.y) * R;
+    const int64_t n = min(int64_t(count[blockIdx.y]), R);
+    for (int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < n; k += int64_t(gridDim.x) * blockDim.x)
+        out_row[base + k] = w.frow[base + index[base + k]];
+}
+
+}  // namespace
+}  // namespace ym
+
+// (class_aware: the sorted labels belong to the bitmask path, which unnormalised boxes never take: the same size)
+extern "C" size_t ym_decode_nms_tiles_workspace_size(int64_t G, int64_t R, int class_aware) {
+    (void)class_aware;
+    return tiles_ws_bytes(std::max<int64_t>(G, 0), std::max<int64_t>(R, 1));
+}
+
+extern "C" int ym_decode_nms_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
+                                   int64_t tile_stride, int64_t col_stride, const ym_tile_entry* table_dev,
+                                   const int64_t* tile_begin, int64_t G, float conf, float iou_thr, float edge,
+                                   int class_aware, int max_det, void* workspace, size_t workspace_bytes,
+                                   int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels,
+                                   int64_t* out_index, int64_t* out_row, void* stream) {
+    YM_CHECK_ARG(G >= 0 && G <= 65535 * int64_t(TILE_SPAN), "ym_decode_nms_tiles: G=%lld", (long long)G);
+    YM_CHECK_ARG(max_det >= 0, "ym_decode_nms_tiles: max_det %d < 0", max_det);
+    YM_CHECK_ARG(max_det == 0 || class_aware, "ym_decode_nms_tiles: max_det needs class_aware");
+    YM_CHECK_ARG(edge == edge, "ym_decode_nms_tiles: edge is NaN");
+    YM_CHECK_ARG(T >= 0 && T <= INT32_MAX && N >= 0 && N < (int64_t(1) << 30) && C >= 1,
+                 "ym_decode_nms_tiles: bad shape T=%lld N=%lld C=%lld", (long long)T, (long long)N, (long long)C);
+    YM_CHECK_ARG(col_stride >= 1 && (col_stride > 1 || row_stride >= 4 + C), "ym_decode_nms_tiles: row_stride < 4+C");
+    YM_CHECK_ARG(tile_begin && tile_begin[0] >= 0, "ym_decode_nms_tiles: tile_begin");
+    int64_t most = 0;
+    for (int64_t g = 0; g < G; ++g) {
+        YM_CHECK_ARG(tile_begin[g + 1] >= tile_begin[g], "ym_decode_nms_tiles: tile_begin is not monotone at %lld",
+                     (long long)g);
+        most = std::max(most, tile_begin[g + 1] - tile_begin[g]);
+    }
+    YM_CHECK_ARG(tile_begin[G] <= T, "ym_decode_nms_tiles: tile_begin[G]=%lld > T=%lld", (long long)tile_begin[G],
+                 (long long)T);
+    const int64_t R = N * most;                              // < 2^61: both factors were bounded above
+    YM_CHECK_ARG(R < (int64_t(1) << 30), "ym_decode_nms_tiles: R=%lld too large", (long long)R);
+    if (G == 0) return YM_OK;
+    YM_CHECK_ARG(out_count, "ym_decode_nms_tiles: out_count is NULL");
+    hipStream_t st = as_stream(stream);
+    if (R == 0) return hipMemsetAsync(out_count, 0, G * sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
+    YM_CHECK_ARG(pred && table_dev && workspace && out_boxes && out_scores && out_labels && out_index,
+                 "ym_decode_nms_tiles: NULL argument");
+    const size_t need = tiles_ws_bytes(G, R);
+    YM_CHECK_ARG(workspace_bytes >= need, "ym_decode_nms_tiles: workspace too small (%zu < %zu)", workspace_bytes, need);
+    Ws w = carve_tiles(workspace, G, R);
+    for (int64_t g0 = 0; g0 < G; g0 += TILE_SPAN) {
+        const int ng = int(std::min<int64_t>(TILE_SPAN, G - g0));
+        TileSpan span = {};
+        for (int k = 0; k <= ng; ++k) span.begin[k] = int32_t(tile_begin[g0 + k]);
+        if (C <= 64)
+            hipLaunchKernelGGL(rowmax_tiles_thread_kernel, dim3(unsigned((R + 255) / 256), unsigned(ng)), dim3(256), 0,
+                               st, pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge,
+                               w);
+        else
+            hipLaunchKernelGGL(rowmax_tiles_wave_kernel, dim3(unsigned((R + 3) / 4), unsigned(ng)), dim3(256), 0, st,
+                               pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge, w);
+    }
+    YM_LAUNCH_CHECK("rowmax tiles");
+    const int rc = launch_nms(G, R, iou_thr, 1.0f, 1.0f, 0, w, out_count, out_boxes, out_scores, out_labels, out_index,
+                              st, class_aware != 0, max_det);
+    if (rc != YM_OK || !out_row) return rc;
+    hipLaunchKernelGGL(tile_rows_kernel, dim3(unsigned(std::min<int64_t>((R + 255) / 256, 64)), unsigned(G)),
+                       dim3(256), 0, st, R, w, out_count, out_index, out_row);
+    YM_LAUNCH_CHECK("tile_rows_kernel");
+    return YM_OK;
+}

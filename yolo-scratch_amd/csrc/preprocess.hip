@@ -28,6 +28,9 @@
 // Letterbox (ym_letterbox_u8c, ym_unletterbox_boxes): the same launch shape once more, with a per-image
 // table entry (ym_lb_entry) the host computed — the resized size, where it sits in the frame, and the fp32 factors back
 // to source pixels.  The device derives no geometry; the pad takes the fill and reads no source byte.
+//
+// Tiles (ym_slice_letterbox_u8c): the letterbox launch shape over a table of windows (ym_tile_entry) into
+// sources that were uploaded once; a tile is the letterbox of its window taken as an image of its own.
 #include <algorithm>
 
 #include "common.h"
@@ -216,6 +219,60 @@ __global__ void letterbox_u8c_kernel(const uint8_t* __restrict__ src, const int6
     }
 }
 
+// ym_tile_sample_c (include/yolomi_augment.h) in letterbox_u8c_kernel's launch shape: out (T, CH, H, W) fp32.
+// blockIdx.y walks tiles, so the entry, its validity, the window's first byte and the copy / resize choice are
+// block-uniform.  The window is addressed as an image whose rows lie the source's pitch apart; a tile that is not valid
+// (ym_tile_valid) takes the fill and touches no source byte, so a wrong table cannot cause a read outside an image.
+template <int CH>
+__global__ void slice_letterbox_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                           int n_images, const ym_tile_entry* __restrict__ table, int n_tiles, int H,
+                                           int W, float fill, int vec, float* __restrict__ out) {
+    const int HW = H * W;
+    const int groups = (HW + 3) >> 2;
+    for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+        const ym_tile_entry e = table[t];
+        const bool valid = ym_tile_valid(meta, n_images, &e);
+        const bool copy = e.nw == e.tw && e.nh == e.th;
+        int64_t pitch = 0;
+        const uint8_t* win = src;
+        if (valid) {
+            pitch = meta[3 * int64_t(e.src) + 2] * CH;
+            win = src + meta[3 * int64_t(e.src)] + e.y0 * pitch + int64_t(e.x0) * CH;
+        }
+        const double fx = valid ? double(e.tw) / e.nw : 0.0, fy = valid ? double(e.th) / e.nh : 0.0;
+        float* o = out + int64_t(t) * CH * HW;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / W, x = p - y * W;
+            float v[CH][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t u = int64_t(x) - e.left, w = int64_t(y) - e.top;
+                if (p + k < HW && valid && u >= 0 && u < e.nw && w >= 0 && w < e.nh) {
+                    if (copy) {
+                        const uint8_t* px = win + w * pitch + u * CH;
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(px[c]) / 255.0f;
+                    } else {
+                        int sx, a0, a1, sy, b0, b1;
+                        ym_aug_lin_coeff(int(u), fx, e.tw, sx, a0, a1);
+                        ym_aug_lin_coeff(int(w), fy, e.th, sy, b0, b1);
+                        ym_aug_taps tp;
+                        ym_aug_set_taps_pitch(win, e.th, e.tw, CH, pitch, sx, a0, a1, sy, b0, b1, tp);
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) v[c][k] = float(ym_aug_taps_value(tp, c)) / 255.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) v[c][k] = fill;
+                }
+                if (++x == W) { x = 0; ++y; }
+            }
+            store_planes<CH>(o, HW, p, vec, v);
+        }
+    }
+}
+
 // one thread per box; blockIdx.y walks images (entry and count through scalar loads)
 __global__ void unletterbox_boxes_kernel(const float4* __restrict__ boxes, const int32_t* __restrict__ count,
                                          const ym_lb_entry* __restrict__ table, int batch, int64_t N, float fw,
@@ -377,6 +434,32 @@ extern "C" int ym_letterbox_u8c(const uint8_t* src, const int64_t* meta, const y
     }
 #undef YM_LETTERBOX_C
     YM_LAUNCH_CHECK("ym_letterbox_u8c");
+    return YM_OK;
+}
+
+extern "C" int ym_slice_letterbox_u8c(const uint8_t* src, const int64_t* meta, int n_images,
+                                      const ym_tile_entry* table_dev, int n_tiles, int ch, int out_h, int out_w,
+                                      int fill, float* out, void* stream) {
+    YM_CHECK_ARG(src && meta && table_dev && out && n_images >= 0 && n_tiles >= 0 && out_h > 0 && out_h <= 32768 &&
+                     out_w > 0 && out_w <= 32768 && ch >= 1 && ch <= 4,
+                 "ym_slice_letterbox_u8c: bad arguments (ch is 1..4, out_h and out_w 1..32768)");
+    if (n_tiles == 0) return YM_OK;
+    const int64_t hw = int64_t(out_h) * out_w;
+    const int64_t groups = (hw + 3) / 4;
+    const dim3 grid(unsigned(std::min<int64_t>((groups + 255) / 256, 256)), unsigned(std::min(n_tiles, 65535)));
+    const int vec = hw % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const float fv = float(fill & 255) / 255.0f;
+#define YM_SLICE_C(CH)                                                                                            \
+    hipLaunchKernelGGL(slice_letterbox_u8c_kernel<CH>, grid, dim3(256), 0, as_stream(stream), src, meta, n_images, \
+                       table_dev, n_tiles, out_h, out_w, fv, vec, out)
+    switch (ch) {
+        case 1: YM_SLICE_C(1); break;
+        case 2: YM_SLICE_C(2); break;
+        case 3: YM_SLICE_C(3); break;
+        default: YM_SLICE_C(4); break;
+    }
+#undef YM_SLICE_C
+    YM_LAUNCH_CHECK("ym_slice_letterbox_u8c");
     return YM_OK;
 }
 

@@ -7,7 +7,8 @@ is the training-time replacement of prepare_batch that augments on the GPU; Yolo
 reads images/ + labels/*.txt datasets of 1, 3 or 4 planes through the same collate and the same two launches;
 datasets/letterbox.py keeps the aspect ratio instead of stretching (collate_fn_cuda(letterbox=True)) and maps boxes
 between the source image and the letterboxed frame; with rect=True the frame is the batch's minimal stride-multiple
-rectangle, and RectSampler (datasets/rect.py) walks a val set by aspect ratio.
+rectangle, and RectSampler (datasets/rect.py) walks a val set by aspect ratio; datasets/slicing.py plans the
+overlapping full-resolution windows of sliced inference and cuts them on the GPU.
 """
 from .collate import collate_fn_cuda  # noqa: F401
 from .crater import CraterDatasetCUDA, max_gt_count, prepare_batch, resize_batch  # noqa: F401

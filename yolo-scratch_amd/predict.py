@@ -2,6 +2,7 @@
 
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --scale s --ch 3 --nc 80 --ema
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source video_frames/ --ch 3 --nc 80 --rect
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source orbital_frames/ --slice 640 --slice-edge 4
 
 Per image `<save-dir>/<stem>.txt` with rows `cls cx cy w h conf` normalised to the source image (the label format of
 datasets/yolo_txt.py plus the confidence), and one `<save-dir>/predictions.json` with the pixel boxes.  The images
@@ -42,8 +43,26 @@ def build_parser():
     ap.add_argument("--rect", action="store_true",
                     help="run each image in its minimal multiple-of-32 frame instead of the --imgsz square (--imgsz "
                          "must be a multiple of 32); the files are walked by aspect ratio so batches share a frame")
+    ap.add_argument("--slice", type=int, default=0, metavar="TILE",
+                    help="sliced inference: run the network on overlapping TILE x TILE windows at full resolution and "
+                         "merge their boxes in one NMS per image (0: off; not with --rect)")
+    ap.add_argument("--slice-overlap", type=float, default=0.2, help="share of a window's side that neighbours overlap")
+    ap.add_argument("--no-slice-full", dest="slice_full", action="store_false",
+                    help="skip the extra pass over the whole image (it sees objects larger than a window)")
+    ap.add_argument("--slice-edge", type=float, default=0.0,
+                    help="drop a window's boxes within this many pixels of a window side inside the image (0: none)")
     ap.add_argument("--save-dir", type=str, default="runs/predict")
     return ap
+
+
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.slice < 0:
+        ap.error("--slice is a window size in pixels")
+    if args.slice and args.rect:
+        ap.error("--slice and --rect exclude each other")
+    return args
 
 
 def find_images(source):
@@ -74,16 +93,20 @@ def header_ratio(path):
 
 
 def txt_rows(det, h0, w0):
-    """`cls cx cy w h conf` rows, normalised to the h0 x w0 source image."""
+    """`cls cx cy w h conf` rows, normalised to the h0 x w0 source image.  A label row has no negative size: a box
+    whose corners come out in reverse is written by its extent; predictions.json keeps the corners as they are.
+    (The trainer initialises the DFL conv weight at random like every conv's, as the reference does, and it is
+    frozen: where its mean is negative, a barely trained head decodes negative distances.)"""
     rows = []
     for (x1, y1, x2, y2), s, c in zip(det["boxes"].tolist(), det["scores"].tolist(), det["labels"].tolist()):
+        x1, x2, y1, y2 = min(x1, x2), max(x1, x2), min(y1, y2), max(y1, y2)
         rows.append(f"{int(c)} {(x1 + x2) / 2 / w0:.6f} {(y1 + y2) / 2 / h0:.6f} {(x2 - x1) / w0:.6f} "
                     f"{(y2 - y1) / h0:.6f} {s:.6f}")
     return rows
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("yolomi runs on MI355X GPUs only (no CPU fallback)")
     device = torch.device("cuda", 0)
@@ -94,7 +117,8 @@ def main(argv=None):
     key = T.load_checkpoint(args.weights, model, device, ema=args.ema)
     print(f"Loaded {key} from {args.weights}")
     predictor = Predictor(model, imgsz=args.imgsz, ch=args.ch, conf=args.conf, iou=args.iou, max_det=args.max_det,
-                          class_aware=True, device=device, batch=args.batch, rect=args.rect)
+                          class_aware=True, device=device, batch=args.batch, rect=args.rect, slice=args.slice,
+                          slice_overlap=args.slice_overlap, slice_full=args.slice_full, slice_edge=args.slice_edge)
     save_dir = Path(args.save_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     order = list(range(len(files)))

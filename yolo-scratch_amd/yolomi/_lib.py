@@ -78,6 +78,12 @@ class LbEntry(ctypes.Structure):
                 ("sy", F32)]
 
 
+class TileEntry(ctypes.Structure):
+    """ym_tile_entry (include/yolomi.h): one window of a sliced image and its letterbox geometry."""
+    _fields_ = [("src", I32), ("x0", I32), ("y0", I32), ("tw", I32), ("th", I32), ("nw", I32), ("nh", I32),
+                ("left", I32), ("top", I32), ("edges", I32), ("sx", F32), ("sy", F32)]
+
+
 R = _c.c_int
 # name -> (restype, argtypes); must match include/yolomi.h + include/yolomi_experimental.h (the setters of the kernel
 # variants measured and rejected in rounds 5 / 6 went with their code: DESIGN §12 / §13, profiles/r05, profiles/r06; the code
@@ -194,6 +200,10 @@ SIGNATURES = {
     "ym_augment_u8c": (R, [P, P, P, P, INT, INT, INT, P, P]),
     "ym_letterbox_u8c": (R, [P, P, P, INT, INT, INT, INT, INT, P, P]),
     "ym_unletterbox_boxes": (R, [P, P, P, I64, I64, INT, INT, P, P]),
+    "ym_slice_letterbox_u8c": (R, [P, P, INT, P, INT, INT, INT, INT, INT, P, P]),
+    "ym_decode_nms_tiles_workspace_size": (SZ, [I64, I64, INT]),
+    "ym_decode_nms_tiles": (R, [P, I64, I64, I64, I64, I64, I64, P, P, I64, F32, F32, F32, INT, INT, P, SZ, P, P, P,
+                                P, P, P, P]),
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),

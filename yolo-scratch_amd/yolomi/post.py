@@ -109,3 +109,49 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
     if padded:
         return {"boxes": boxes, "scores": scores, "labels": labels, "count": cnt, "counts": counts}
     return [{"boxes": boxes[b, :k], "scores": scores[b, :k], "labels": labels[b, :k]} for b, k in enumerate(counts)]
+
+
+def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, conf: float, iou_thr: float,
+                     class_aware: bool = False, max_det: int = 0, edge: float = 0.0):
+    """Decode + NMS of sliced inference (ym_decode_nms_tiles): pred read as (T, N, 4+C), one slice per
+    tile; `table_dev` the device table of ym_tile_entry (uint8 bytes, at least T entries); `tile_begin` the G + 1
+    host values that give image g the tiles [tile_begin[g], tile_begin[g + 1]).  Every tile's candidates are mapped
+    to source pixels, those a tile border cuts within `edge` pixels are dropped (0: none), and one NMS runs per
+    image over the rest.
+
+    Returns the padded dict of decode_nms(..., padded=True) with R = N * (the largest tile count) rows per image and
+    "boxes" in source pixels (xyxy, unnormalised), plus "rows" (G, R) int64: the row of the image's (tile, row)
+    concatenation a kept box came from, tile = row // N."""
+    import ctypes
+    from ._lib import TileEntry, lib
+    require_device(pred, table_dev)
+    p = pred.float()
+    if p.stride(-1) < 1:
+        p = p.contiguous()
+    T, N, W = p.shape
+    C = W - 4
+    dev = p.device
+    begin = [int(v) for v in tile_begin]
+    G = len(begin) - 1
+    if G < 0:
+        raise ValueError("decode_nms_tiles: tile_begin holds G + 1 values")
+    if max_det and not class_aware:
+        raise ValueError("decode_nms_tiles: max_det needs class_aware=True (the class-agnostic path has no cap)")
+    assert table_dev.dtype == torch.uint8 and table_dev.numel() >= T * ctypes.sizeof(TileEntry)
+    most = max([b - a for a, b in zip(begin, begin[1:])] + [0])
+    R = max(N * most, 0)
+    cb = (ctypes.c_int64 * (G + 1))(*begin)
+    ws_bytes = lib().ym_decode_nms_tiles_workspace_size(G, max(R, 1), int(class_aware))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    cnt = torch.empty(G, dtype=torch.int32, device=dev)          # every count is written by the launch
+    boxes = torch.empty(G, R, 4, dtype=torch.float32, device=dev)
+    scores = torch.empty(G, R, dtype=torch.float32, device=dev)
+    labels = torch.empty(G, R, dtype=torch.int64, device=dev)
+    index = torch.empty(G, R, dtype=torch.int64, device=dev)
+    rows = torch.empty(G, R, dtype=torch.int64, device=dev)
+    call("ym_decode_nms_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
+         float(conf), float(iou_thr), float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes, ptr(cnt),
+         ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), stream_ptr(dev))
+    counts = cnt.cpu().tolist()                      # the single host sync of the group
+    return {"boxes": boxes, "scores": scores, "labels": labels, "count": cnt, "counts": counts, "index": index,
+            "rows": rows}

@@ -11,6 +11,11 @@ The host synchronises once per batch, for the per-image counts.
 `rect=True`: every image gets its own minimal multiple-of-32 frame (datasets.letterbox.rect_frame) in
 place of the imgsz x imgsz square, images are grouped by frame, and the four steps run per group at (H, W); the
 results come back in input order.
+
+`slice=TILE`: sliced inference.  The sources of a group are packed and uploaded once; the network runs on
+their overlapping TILE x TILE windows at full resolution (datasets.slicing), each letterboxed into the imgsz x imgsz
+frame by ym_slice_letterbox_u8c, `batch` tiles per forward; ym_decode_nms_tiles maps every tile's candidates into
+source pixels and runs one NMS per source image, so there is no unletterbox step.  One host sync per group.
 """
 from __future__ import annotations
 
@@ -28,11 +33,15 @@ class Predictor:
     cap.  `batch`: the fixed batch size of the forward; more images run in several batches.  `rect`: rectangular
     frames, one per image shape (imgsz must be a multiple of 32); images of one frame run together in chunks of
     `batch`, so the plan and graph of (batch, H, W) replay, and the eval plans of at most `max_frames`
-    most-recently-used frames are kept (yolomi.graph.FrameLRU).  Without `rect` nothing is ever dropped."""
+    most-recently-used frames are kept (yolomi.graph.FrameLRU).  Without `rect` nothing is ever dropped.
+    `slice`: sliced inference on slice x slice windows that share `slice_overlap` of their side; `slice_full`: one more
+    pass over the whole image, for objects larger than a tile; `slice_edge` > 0: a tile's boxes within that many
+    pixels of a window side that is not an image side are left to the neighbouring tile.  Not with `rect`."""
 
     def __init__(self, model, imgsz: int = 640, ch: int | None = None, conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114,
-                 rect: bool = False, max_frames: int = 8):
+                 rect: bool = False, max_frames: int = 8, slice: int = 0, slice_overlap: float = 0.2,
+                 slice_full: bool = True, slice_edge: float = 0.0):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise YolomiError("Predictor runs on the MI355X only (no CPU fallback)")
@@ -46,6 +55,15 @@ class Predictor:
         if self.batch < 1 or self.imgsz < 1:
             raise ValueError("Predictor: batch and imgsz are at least 1")
         self.rect, self._lru = bool(rect), None
+        self.slice, self.slice_overlap = int(slice), float(slice_overlap)
+        self.slice_full, self.slice_edge = bool(slice_full), float(slice_edge)
+        if self.slice < 0:
+            raise ValueError("Predictor: slice is a tile size in pixels (0: off)")
+        if self.slice:
+            if rect:
+                raise ValueError("Predictor: slice and rect exclude each other (tiles run in the imgsz x imgsz frame)")
+            from datasets.slicing import slice_step
+            slice_step(self.slice, self.slice_overlap)               # raises on an overlap that leaves no step
         if self.rect:
             from datasets.letterbox import rect_frame
             from .graph import FrameLRU
@@ -94,6 +112,39 @@ class Predictor:
                                 padded=True)
         return unletterbox(dets, table, H, W)[:len(images)]
 
+    @torch.no_grad()
+    def _run_sliced(self, images):
+        """Up to `batch` sources: one upload, the tiles `batch` at a time through the slice kernel and the eval
+        forward (the last chunk padded with src = -1 tiles, so the plan and graph of (batch, imgsz, imgsz) replay),
+        every chunk's output copied into one (T, 4 + nc, A) buffer, then one ym_decode_nms_tiles and its sync."""
+        from datasets.crater import pack_images
+        from datasets.slicing import slice_batch, tile_bytes, tile_table
+        raw = [self._raw(im) for im in images]
+        packed = pack_images(raw, self.imgsz, self.ch)
+        S, nb = self.imgsz, self.batch
+        table, begin = tile_table(packed["img_meta"][:, 1:].tolist(), self.slice, self.slice_overlap, S,
+                                  self.slice_full)
+        T = begin[-1]
+        if T == 0:
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.device)    # noqa: E731
+            return [{"boxes": z(0, 4), "scores": z(0), "labels": z(0, dt=torch.int64)} for _ in images]
+        Tp = -(-T // nb) * nb
+        mv = lambda t: t.to(self.device, non_blocking=True)          # noqa: E731
+        tdev = mv(tile_bytes(table, T, Tp).pin_memory())
+        u8, meta = mv(packed["img_u8"]), mv(packed["img_meta"])
+        ybuf = None
+        for lo in range(0, Tp, nb):
+            img = slice_batch(u8, meta, tdev, nb, S, S, self.ch, self.fill, first=lo)
+            y = self.model(img)[0]                                   # (batch, 4 + nc, A)
+            if ybuf is None:
+                ybuf = torch.empty(Tp, *y.shape[1:], dtype=y.dtype, device=y.device)
+            ybuf[lo:lo + nb].copy_(y)                                # before the next replay overwrites it
+        d = _post.decode_nms_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou,
+                                   class_aware=self.class_aware, max_det=self.max_det if self.class_aware else 0,
+                                   edge=self.slice_edge)
+        return [{"boxes": d["boxes"][g, :k], "scores": d["scores"][g, :k], "labels": d["labels"][g, :k]}
+                for g, k in enumerate(d["counts"])]
+
     def frame_of(self, im):
         """(H, W) of one image's rectangular frame."""
         from datasets.letterbox import rect_frame
@@ -116,5 +167,5 @@ class Predictor:
             return out
         out = []
         for lo in range(0, len(images), self.batch):
-            out += self._run(images[lo:lo + self.batch])
+            out += (self._run_sliced if self.slice else self._run)(images[lo:lo + self.batch])
         return out
