@@ -645,7 +645,7 @@ WgPlan wg_plan(const ym_conv_desc* d, int wg_target) {
     int64_t splits = std::max<int64_t>(1, std::min<int64_t>(target / cols, p.units / min_units));
     splits = std::min<int64_t>(splits, p.kind == 0 ? 65535 : 256);
     if (p.kind != 0 && splits >= 8) splits &= ~int64_t(7);      // whole XCD groups (wg_tile)
-    p.chunk = (p.units + splits - 1) / splits;
+    p.chunk = std::max<int64_t>(1, (p.units + splits - 1) / splits);      // an empty batch has no units
     p.splits = std::max<int64_t>(1, (p.units + p.chunk - 1) / p.chunk);
     return p;
 }
