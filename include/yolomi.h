@@ -555,6 +555,22 @@ int ym_resize_linear_u8c(const uint8_t* src, const int64_t* meta, int batch, int
 int ym_augment_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
                    const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out, void* stream);
 
+/* ym_augment_u8c with MixUp in the launch.  Image b is mixed when mix_dev[b].partner names an entry of `partner_dev`,
+ * a compact table of n_partner second entries (only the mixed images carry one): both entries are sampled at every
+ * output pixel, each with its own fill, tiles, maps and YM_AUG_STRETCH flag, and blended per plane before hue / sat
+ * and gain as v = (a * r + p * (65536 - r)) >> 16 with r = `ratio` clamped to [0, 65536]
+ * (include/yolomi_augment.h: ym_aug_mix_sample_c).  Hue / sat (colour_dev[b]) and the gain then act on the blend;
+ * the gain is table_dev[b]'s, the partner entry's `gain` is ignored.  A `partner` outside [0, n_partner), -1 by
+ * convention, leaves image b what ym_augment_u8c makes of it bit for bit and reads nothing from `partner_dev`, which
+ * may be NULL when n_partner == 0.  Every other argument, and every argument error, is ym_augment_u8c's. */
+typedef struct ym_aug_mix {
+    int32_t ratio;             /* Q16 weight of the primary image, clamped to [0, 65536] */
+    int32_t partner;           /* index into partner_dev; outside [0, n_partner): this image is not mixed */
+} ym_aug_mix;
+int ym_augment_mix_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
+                       const ym_aug_entry* partner_dev, int n_partner, const ym_aug_mix* mix_dev,
+                       const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out, void* stream);
+
 /* Letterbox: the aspect ratio kept.  Image b is resized (the rule of ym_resize_linear_u8c) to nw x nh pixels and
  * placed with its first pixel at (left, top) of an out_w x out_h frame whose other pixels are `fill`.  The host
  * computes the geometry in fp64 (datasets/letterbox.py: letterbox_geometry) and hands it over in this table, one

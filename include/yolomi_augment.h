@@ -328,4 +328,67 @@ YM_HD static inline void ym_aug_sample_c(const uint8_t* src, const int64_t* meta
     ym_aug_planes(e, col, ch, hit, t, v);
 }
 
+/* ---------------------------------------------------------------- MixUp (ym_augment_mix_u8c)
+ * A mixed image is two entries sampled at the same output pixel, the primary's a[c] and the partner's p[c], both
+ * before hue / sat and gain, blended in integers:
+ *   v[c] = (a[c] * r + p[c] * (65536 - r)) >> 16      r Q16, clamped to [0, 65536]; at most 255 * 65536, an int32
+ * a == p returns a; r = 65536 returns a and r = 0 returns p; v lies between the two and is the real-valued blend
+ * truncated (0 <= real - v < 1), as Ultralytics' (a * r + b * (1 - r)).astype(uint8).  Hue / sat (the image's colour
+ * entry) and the gain follow on the blended planes, as Ultralytics applies HSV after MixUp; the gain is the PRIMARY
+ * entry's and the partner entry's `gain` is ignored.  An image without a partner is ym_aug_sample_c bit for bit. */
+static_assert(sizeof(ym_aug_mix) == 8, "ym_aug_mix layout (yolomi/_lib.py)");
+
+/* ym_aug_sample_c's geometry for either kind of entry; false: the pixel shows the fill */
+YM_HD static inline bool ym_aug_entry_taps(const uint8_t* src, const int64_t* meta, int batch, int ch, int S,
+                                           const ym_aug_entry* e, int x, int y, ym_aug_taps& t) {
+    if (e->flags & YM_AUG_STRETCH) return ym_aug_stretch_taps(src, meta, batch, ch, S, e, x, y, t);
+    int64_t cx, cy;
+    const int slot = ym_aug_slot(e, x, y, cx, cy);
+    return ym_aug_tile_taps(src, meta, batch, ch, &e->tile[slot], cx, cy, x, y, t);
+}
+
+/* the `ch` planes of a pixel before hue / sat and gain: the tap blend, or the entry's fill */
+YM_HD static inline void ym_aug_raw_planes(const ym_aug_entry* e, int ch, bool hit, const ym_aug_taps& t, int* v) {
+    for (int c = 0; c < ch; ++c) v[c] = hit ? ym_aug_taps_value(t, c) : (e->fill & 255);
+}
+
+YM_HD static inline int ym_aug_mix_ratio(int r) { return r < 0 ? 0 : (r > 65536 ? 65536 : r); }
+
+/* a, p in 0..255, r = ym_aug_mix_ratio(.) */
+YM_HD static inline int ym_aug_mix_blend(int a, int p, int r) { return (a * r + p * (65536 - r)) >> 16; }
+
+/* true: `mix` names an entry of the partner table; false: the image is not mixed and that table is not read */
+YM_HD static inline bool ym_aug_mix_valid(const ym_aug_mix* mix, int n_partner) {
+    return mix && mix->partner >= 0 && mix->partner < n_partner;
+}
+
+/* blended planes `a` (in: the primary's raw planes) and `p` (the partner's) -> a: blend, hue / sat, primary gain */
+YM_HD static inline void ym_aug_mix_planes(const ym_aug_entry* e, const ym_aug_colour* col, int ch, int ratio,
+                                           const int* p, int* a) {
+    const int r = ym_aug_mix_ratio(ratio);
+    for (int c = 0; c < ch; ++c) a[c] = ym_aug_mix_blend(a[c], p[c], r);
+    if (col && ch == 3) ym_aug_hue_sat(col->hue, col->sat, a);
+    for (int c = 0; c < ch; ++c) a[c] = ym_aug_gain(e->gain, a[c]);
+}
+
+/* the `ch` values v[0..ch) of output pixel (x, y) of the image whose primary entry is `e`, mix record `mix` (may be
+ * null) and colour entry `col` (may be null); `partner` is the compact table of n_partner second entries */
+YM_HD static inline void ym_aug_mix_sample_c(const uint8_t* src, const int64_t* meta, int batch, int ch, int S,
+                                             const ym_aug_entry* e, const ym_aug_mix* mix,
+                                             const ym_aug_entry* partner, int n_partner, const ym_aug_colour* col,
+                                             int x, int y, int* v) {
+    if (!ym_aug_mix_valid(mix, n_partner)) {
+        ym_aug_sample_c(src, meta, batch, ch, S, e, col, x, y, v);
+        return;
+    }
+    const ym_aug_entry* pe = partner + mix->partner;
+    ym_aug_taps t = {};
+    int w[4];
+    bool hit = ym_aug_entry_taps(src, meta, batch, ch, S, e, x, y, t);
+    ym_aug_raw_planes(e, ch, hit, t, v);
+    hit = ym_aug_entry_taps(src, meta, batch, ch, S, pe, x, y, t);
+    ym_aug_raw_planes(pe, ch, hit, t, w);
+    ym_aug_mix_planes(e, col, ch, mix->ratio, w, v);
+}
+
 #endif

@@ -344,6 +344,78 @@ __global__ void augment_u8c_kernel(const uint8_t* __restrict__ src, const int64_
     }
 }
 
+// ---- MixUp (ym_augment_mix_u8c): augment_u8c_kernel's launch shape with a second, compact table of
+// partner entries.  The mix record is block-uniform like the entry, so the choice between the two pixel functions
+// below is a scalar branch; an image that is not mixed runs augment_pixel_c and never forms a partner address.
+
+// ym_aug_entry_taps for a block-uniform entry `e`, with augment_pixel's wave-uniform-slot path
+template <int CH>
+__device__ __forceinline__ bool augment_taps_c(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                               int batch, int S, const ym_aug_entry* __restrict__ e, int x, int y,
+                                               ym_aug_taps& t) {
+    if (e->flags & YM_AUG_STRETCH) return ym_aug_stretch_taps(src, meta, batch, CH, S, e, x, y, t);
+    int64_t cx, cy;
+    const int slot = ym_aug_slot(e, x, y, cx, cy);
+    const int first = __builtin_amdgcn_readfirstlane(slot);
+    if (__all(slot == first)) return ym_aug_tile_taps(src, meta, batch, CH, &e->tile[first], cx, cy, x, y, t);
+    return ym_aug_tile_taps(src, meta, batch, CH, &e->tile[slot], cx, cy, x, y, t);
+}
+
+// ym_aug_mix_sample_c of a mixed image: the two entries one after the other through one ym_aug_taps, each with its
+// own slot vote
+template <int CH>
+__device__ __forceinline__ void augment_mix_pixel_c(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                                    int batch, int S, const ym_aug_entry* __restrict__ e,
+                                                    const ym_aug_entry* __restrict__ pe, int ratio,
+                                                    const ym_aug_colour* __restrict__ col, int x, int y, int* v) {
+    ym_aug_taps t = {};
+    int w[CH];
+    bool hit = augment_taps_c<CH>(src, meta, batch, S, e, x, y, t);
+    ym_aug_raw_planes(e, CH, hit, t, v);
+    hit = augment_taps_c<CH>(src, meta, batch, S, pe, x, y, t);
+    ym_aug_raw_planes(pe, CH, hit, t, w);
+    ym_aug_mix_planes(e, col, CH, ratio, w, v);
+}
+
+// out (B, CH, S, S) fp32; `partner` n_partner entries (may be null when 0), `mix` one record per image; the rest as
+// for augment_u8c_kernel
+template <int CH>
+__global__ void augment_mix_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
+                                       const ym_aug_entry* __restrict__ table,
+                                       const ym_aug_entry* __restrict__ partner, int n_partner,
+                                       const ym_aug_mix* __restrict__ mix, const ym_aug_colour* __restrict__ colour,
+                                       int batch, int S, int vec, float* __restrict__ out) {
+    const int SS = S * S;
+    const int groups = (SS + 3) >> 2;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const ym_aug_entry* e = table + b;
+        const ym_aug_colour* col = CH == 3 && colour ? colour + b : nullptr;
+        const bool mixed = ym_aug_mix_valid(mix + b, n_partner);
+        const ym_aug_entry* pe = mixed ? partner + mix[b].partner : e;      // e: never read, and inside a table
+        const int ratio = mix[b].ratio;
+        float* o = out + int64_t(b) * CH * SS;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+            const int p = g << 2;
+            int y = p / S, x = p - y * S;
+            float v[CH][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int u[CH] = {};
+                if (p + k < SS) {
+                    if (mixed)
+                        augment_mix_pixel_c<CH>(src, meta, batch, S, e, pe, ratio, col, x, y, u);
+                    else
+                        augment_pixel_c<CH>(src, meta, batch, S, e, col, x, y, u);
+                }
+#pragma unroll
+                for (int c = 0; c < CH; ++c) v[c][k] = float(u[c]) / 255.0f;
+                if (++x == S) { x = 0; ++y; }
+            }
+            store_planes<CH>(o, SS, p, vec, v);
+        }
+    }
+}
+
 }  // namespace
 }  // namespace ym
 
@@ -498,5 +570,32 @@ extern "C" int ym_augment_u8c(const uint8_t* src, const int64_t* meta, const ym_
     }
 #undef YM_AUGMENT_C
     YM_LAUNCH_CHECK("ym_augment_u8c");
+    return YM_OK;
+}
+
+extern "C" int ym_augment_mix_u8c(const uint8_t* src, const int64_t* meta, const ym_aug_entry* table_dev,
+                                  const ym_aug_entry* partner_dev, int n_partner, const ym_aug_mix* mix_dev,
+                                  const ym_aug_colour* colour_dev, int batch, int ch, int size, float* out,
+                                  void* stream) {
+    YM_CHECK_ARG(src && meta && table_dev && mix_dev && out && batch >= 0 && size > 0 && size <= 32768 && ch >= 1 &&
+                     ch <= 4,
+                 "ym_augment_mix_u8c: bad arguments (ch is 1..4)");
+    YM_CHECK_ARG(n_partner >= 0 && (partner_dev || n_partner == 0),
+                 "ym_augment_mix_u8c: n_partner = %d needs a partner table", n_partner);
+    YM_CHECK_ARG(!colour_dev || ch == 3, "ym_augment_mix_u8c: a colour table needs ch == 3 (got %d)", ch);
+    if (batch == 0) return YM_OK;
+    const dim3 grid = image_grid(batch, size);
+    const int vec = planes_vec(size, out);
+#define YM_AUGMENT_MIX_C(CH)                                                                                       \
+    hipLaunchKernelGGL(augment_mix_u8c_kernel<CH>, grid, dim3(256), 0, as_stream(stream), src, meta, table_dev,    \
+                       partner_dev, n_partner, mix_dev, colour_dev, batch, size, vec, out)
+    switch (ch) {
+        case 1: YM_AUGMENT_MIX_C(1); break;
+        case 2: YM_AUGMENT_MIX_C(2); break;
+        case 3: YM_AUGMENT_MIX_C(3); break;
+        default: YM_AUGMENT_MIX_C(4); break;
+    }
+#undef YM_AUGMENT_MIX_C
+    YM_LAUNCH_CHECK("ym_augment_mix_u8c");
     return YM_OK;
 }

@@ -20,6 +20,12 @@ Batches of 2-4 planes (pixel-interleaved images, `img_ch` in the batch dict: dat
 ym_augment_u8c with the same table: the geometry is formed once per pixel, every plane is blended at the same taps and
 takes the gain.  On 3-plane batches `hsv_h` / `hsv_s` add a per-image hue shift and saturation factor (a second table
 of ym_aug_colour, appended to the first for the transfer); their uniforms are drawn after every other one.
+
+MixUp (`mixup`, off by default): with that probability an image is blended with a second, independent mosaic + affine
+sample around another image of the same batch, r ~ Beta(32, 32) the weight of the first.  Both samples are taken in
+the one launch (ym_augment_mix_u8c) and blended per plane in integers before hue / saturation and the gain, which act
+on the blend as in Ultralytics; the flips are the primary's for both, and the partner's kept boxes follow the
+primary's.  Its draws come after the hue / saturation ones; mosaic closing (`no_mosaic_from`) closes it too.
 """
 from __future__ import annotations
 
@@ -30,7 +36,7 @@ import math
 import numpy as np
 import torch
 
-from yolomi._lib import AugColour, AugEntry, AugTile
+from yolomi._lib import AugColour, AugEntry, AugMix, AugTile
 
 FB = 24                        # YM_AUG_FB
 STRETCH = 1                    # YM_AUG_STRETCH
@@ -53,10 +59,11 @@ class AugmentHyp:
     fill: int = 114
     hsv_h: float = 0.0
     hsv_s: float = 0.0
+    mixup: float = 0.0             # probability that an image is blended with a second sample (off by default)
 
     def is_off(self) -> bool:
         return not any((self.mosaic, self.degrees, self.translate, self.scale, self.shear, self.fliplr, self.flipud,
-                        self.gain, self.hsv_h, self.hsv_s))
+                        self.gain, self.hsv_h, self.hsv_s, self.mixup))
 
 
 def _fix(v) -> int:
@@ -235,6 +242,26 @@ def augment_batch(img_u8: torch.Tensor, meta: torch.Tensor, table: torch.Tensor,
     return out
 
 
+def augment_mix_batch(img_u8: torch.Tensor, meta: torch.Tensor, table: torch.Tensor, partner: torch.Tensor | None,
+                      mix: torch.Tensor, img_size: int, channels: int = 1,
+                      colour: torch.Tensor | None = None) -> torch.Tensor:
+    """augment_batch with MixUp in the launch (ym_augment_mix_u8c, for every plane count): `partner` a device table
+    of ym_aug_entry for the mixed images only (None: no image is mixed), `mix` one ym_aug_mix per image, both as uint8
+    bytes."""
+    from yolomi._lib import call, ptr, require_device, stream_ptr
+    require_device(img_u8, meta, table, partner, mix, colour)
+    B = meta.shape[0]
+    assert table.dtype == torch.uint8 and table.numel() == B * ctypes.sizeof(AugEntry)
+    n_partner = 0 if partner is None else partner.numel() // ctypes.sizeof(AugEntry)
+    assert partner is None or (partner.dtype == torch.uint8 and partner.numel() == n_partner * ctypes.sizeof(AugEntry))
+    assert mix.dtype == torch.uint8 and mix.numel() == B * ctypes.sizeof(AugMix)
+    assert colour is None or (colour.dtype == torch.uint8 and colour.numel() == B * ctypes.sizeof(AugColour))
+    out = torch.empty(B, channels, img_size, img_size, dtype=torch.float32, device=img_u8.device)
+    call("ym_augment_mix_u8c", img_u8.data_ptr(), meta.contiguous().data_ptr(), table.data_ptr(), ptr(partner),
+         n_partner, mix.data_ptr(), ptr(colour), B, channels, img_size, out.data_ptr(), stream_ptr(img_u8.device))
+    return out
+
+
 def table_bytes(entries) -> torch.Tensor:
     """ctypes array of AugEntry (or AugColour) -> host uint8 tensor (a copy)."""
     return torch.from_numpy(np.frombuffer(bytes(entries), dtype=np.uint8).copy())
@@ -274,11 +301,27 @@ class BatchAugment:
         gain = 1.0 + (2.0 * torch.rand(B, generator=g, dtype=torch.float64).numpy() - 1.0) * h.gain
         # hue and saturation are taken from the generator last: every other key is what it was before they existed
         hs = 2.0 * torch.rand(B, 2, generator=g, dtype=torch.float64).numpy() - 1.0
-        return {"mosaic": (u[:, 0] < h.mosaic) & mosaic_on, "cx": u[:, 1], "cy": u[:, 2], "partners": partners,
-                "angle": sym(3, h.degrees), "scale": 1.0 + sym(4, h.scale), "shear_x": sym(5, h.shear),
-                "shear_y": sym(6, h.shear), "tx": 0.5 + sym(7, h.translate), "ty": 0.5 + sym(8, h.translate),
-                "fliplr": u[:, 9] < h.fliplr, "flipud": u[:, 10] < h.flipud, "gain": gain,
-                "hue": hs[:, 0] * h.hsv_h, "sat": 1.0 + hs[:, 1] * h.hsv_s}
+        out = {"mosaic": (u[:, 0] < h.mosaic) & mosaic_on, "cx": u[:, 1], "cy": u[:, 2], "partners": partners,
+               "angle": sym(3, h.degrees), "scale": 1.0 + sym(4, h.scale), "shear_x": sym(5, h.shear),
+               "shear_y": sym(6, h.shear), "tx": 0.5 + sym(7, h.translate), "ty": 0.5 + sym(8, h.translate),
+               "fliplr": u[:, 9] < h.fliplr, "flipud": u[:, 10] < h.flipud, "gain": gain,
+               "hue": hs[:, 0] * h.hsv_h, "sat": 1.0 + hs[:, 1] * h.hsv_s}
+        # MixUp comes after hue and saturation for the same reason.  Column 0 of `w` is the mix decision, 1-9 the
+        # partner sample's mosaic decision, centre, angle, scale, shears and translations; then its source image and
+        # its three mosaic partners.  r ~ Beta(32, 32) exactly as X / (X + Y) of two Gamma(32, 1) draws, each the sum
+        # of 32 Exp(1) draws -log(1 - U) of the same generator (an integer shape needs no rejection sampler).
+        w = torch.rand(B, 10, generator=g, dtype=torch.float64).numpy()
+        mix_src = torch.randint(0, max(B, 1), (B,), generator=g).numpy()
+        mix_partners = torch.randint(0, max(B, 1), (B, 3), generator=g).numpy()
+        xy = -torch.log1p(-torch.rand(B, 2, 32, generator=g, dtype=torch.float64)).sum(-1).numpy()
+        symw = lambda col, r: (2.0 * w[:, col] - 1.0) * r        # noqa: E731
+        out.update({"mix": (w[:, 0] < h.mixup) & mosaic_on, "mix_ratio": xy[:, 0] / (xy[:, 0] + xy[:, 1]),
+                    "mix_src": mix_src, "mix_mosaic": (w[:, 1] < h.mosaic) & mosaic_on, "mix_cx": w[:, 2],
+                    "mix_cy": w[:, 3], "mix_partners": mix_partners, "mix_angle": symw(4, h.degrees),
+                    "mix_scale": 1.0 + symw(5, h.scale), "mix_shear_x": symw(6, h.shear),
+                    "mix_shear_y": symw(7, h.shear), "mix_tx": 0.5 + symw(8, h.translate),
+                    "mix_ty": 0.5 + symw(9, h.translate)})
+        return out
 
     def colours(self, B: int, epoch: int, step: int):
         """The batch's ctypes table of AugColour, or None when hue and saturation are both off."""
@@ -287,8 +330,49 @@ class BatchAugment:
         p = self.draw(B, epoch, step)
         return colour_table(p["hue"], p["sat"])
 
+    def _sample(self, ctx, src: int, g: dict, lr: bool, ud: bool, gain: float):
+        """One mosaic + affine sample around image `src` of the batch from the parameter set `g` (mosaic, cx, cy,
+        partners, angle, scale, shear_x, shear_y, tx, ty) under the flips (lr, ud) -> (AugEntry, kept classes,
+        transformed boxes).  The primary and the MixUp partner of an image both come from here."""
+        S, meta, geo, lb_of, rows_of, boxes, cls = ctx
+        mosaic = bool(g["mosaic"])
+        A = affine_matrix(S, 2 * S if mosaic else S, g["angle"], g["scale"], g["shear_x"], g["shear_y"], g["tx"],
+                          g["ty"])
+        if not mosaic and not lr and not ud and np.array_equal(A, np.eye(3)):
+            entry = plain_entry(src, int(meta[src, 1]), int(meta[src, 2]), S, None, gain, self.hyp.fill, lb=lb_of(src))
+            rows = rows_of[src]
+            return entry, cls[rows], boxes[rows]
+        inv = np.linalg.inv(A) @ flip_matrix(S, lr, ud)          # output pixel -> canvas pixel
+        if mosaic:
+            xc, yc = (int(S / 2 + c * S) for c in (g["cx"], g["cy"]))
+            srcs = [src, *(int(b) for b in g["partners"])]
+            entry = mosaic_entry(srcs, [(int(meta[b, 1]), int(meta[b, 2])) for b in srcs], xc, yc, S, inv, gain,
+                                 self.hyp.fill, lbs=[lb_of(b) for b in srcs] if geo is not None else None)
+            parts = []
+            for (ox, oy), b in zip(mosaic_origins(xc, yc, S), srcs):
+                parts.append(np.clip(boxes[rows_of[b]] * S + np.array([ox, oy, ox, oy], np.float64), 0, 2 * S))
+            canvas_boxes = np.concatenate(parts)
+            rows = np.concatenate([rows_of[b] for b in srcs])
+        else:
+            entry = plain_entry(src, int(meta[src, 1]), int(meta[src, 2]), S, inv, gain, self.hyp.fill, lb=lb_of(src))
+            rows = rows_of[src]
+            canvas_boxes = boxes[rows] * S
+        out, keep = transform_boxes(canvas_boxes, A, S, lr, ud)
+        return entry, cls[rows][keep], out
+
+    _GEOMETRY = ("mosaic", "cx", "cy", "partners", "angle", "scale", "shear_x", "shear_y", "tx", "ty")
+
     def plan(self, batch: dict, epoch: int, step: int):
-        """Host side of one batch -> (ctypes table of AugEntry, batch_idx, cls, bboxes, max_gt)."""
+        """Host side of one batch -> (ctypes table of AugEntry, batch_idx, cls, bboxes, max_gt).  With `mixup` the
+        rows of a mixed image are its own kept rows followed by its partner sample's (plan_mix gives the tables)."""
+        return self.plan_mix(batch, epoch, step)[:5]
+
+    def plan_mix(self, batch: dict, epoch: int, step: int):
+        """plan()'s five, then (ctypes table of the mixed images' partner AugEntry, ctypes table of one AugMix per
+        image), or (None, None) when no image of the batch is mixed.  A mixed image's partner is a second, independent
+        mosaic + affine sample around another image of the batch under the primary's flips (Ultralytics flips after
+        the blend); its kept boxes and classes follow the primary's in image i's rows, unweighted.  The partner
+        entry's gain is 1 and is ignored by the kernel: the primary's gain acts on the blend."""
         from .crater import max_gt_count
         meta = batch["img_meta"].numpy()
         S, B = int(batch["img_size"]), int(meta.shape[0])
@@ -301,35 +385,25 @@ class BatchAugment:
         boxes = batch["bboxes"].numpy().astype(np.float64).reshape(-1, 4)
         cls = batch["cls"].numpy()
         rows_of = [np.nonzero(bidx == i)[0] for i in range(B)]
+        ctx = (S, meta, geo, lb_of, rows_of, boxes, cls)
         table = (AugEntry * max(B, 1))()
+        mixed = [i for i in range(B) if p["mix"][i]]
+        partner = (AugEntry * len(mixed))() if mixed else None
+        mix = (AugMix * B)() if mixed else None
         o_idx, o_cls, o_box = [], [], []
         for i in range(B):
             lr, ud, gain = bool(p["fliplr"][i]), bool(p["flipud"][i]), float(p["gain"][i])
-            mosaic = bool(p["mosaic"][i])
-            A = affine_matrix(S, 2 * S if mosaic else S, p["angle"][i], p["scale"][i], p["shear_x"][i], p["shear_y"][i],
-                              p["tx"][i], p["ty"][i])
-            if not mosaic and not lr and not ud and np.array_equal(A, np.eye(3)):
-                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, None, gain, self.hyp.fill, lb=lb_of(i))
-                rows = rows_of[i]
-                o_idx.append(np.full(len(rows), i)), o_cls.append(cls[rows]), o_box.append(boxes[rows])
+            table[i], kept, out = self._sample(ctx, i, {k: p[k][i] for k in self._GEOMETRY}, lr, ud, gain)
+            o_idx.append(np.full(len(out), i)), o_cls.append(kept), o_box.append(out)
+            if mix is None:
                 continue
-            inv = np.linalg.inv(A) @ flip_matrix(S, lr, ud)          # output pixel -> canvas pixel
-            if mosaic:
-                xc, yc = (int(S / 2 + c * S) for c in (p["cx"][i], p["cy"][i]))
-                srcs = [i, *(int(b) for b in p["partners"][i])]
-                table[i] = mosaic_entry(srcs, [(int(meta[b, 1]), int(meta[b, 2])) for b in srcs], xc, yc, S, inv, gain,
-                                        self.hyp.fill, lbs=[lb_of(b) for b in srcs] if geo is not None else None)
-                parts = []
-                for (ox, oy), b in zip(mosaic_origins(xc, yc, S), srcs):
-                    parts.append(np.clip(boxes[rows_of[b]] * S + np.array([ox, oy, ox, oy], np.float64), 0, 2 * S))
-                canvas_boxes = np.concatenate(parts)
-                rows = np.concatenate([rows_of[b] for b in srcs])
-            else:
-                table[i] = plain_entry(i, int(meta[i, 1]), int(meta[i, 2]), S, inv, gain, self.hyp.fill, lb=lb_of(i))
-                rows = rows_of[i]
-                canvas_boxes = boxes[rows] * S
-            out, keep = transform_boxes(canvas_boxes, A, S, lr, ud)
-            o_idx.append(np.full(len(out), i)), o_cls.append(cls[rows][keep]), o_box.append(out)
+            mix[i].ratio, mix[i].partner = 65536, -1
+            if p["mix"][i]:
+                k = mixed.index(i)
+                partner[k], kept, out = self._sample(ctx, int(p["mix_src"][i]),
+                                                     {g: p["mix_" + g][i] for g in self._GEOMETRY}, lr, ud, 1.0)
+                mix[i].ratio, mix[i].partner = int(math.floor(float(p["mix_ratio"][i]) * 65536.0 + 0.5)), k
+                o_idx.append(np.full(len(out), i)), o_cls.append(kept), o_box.append(out)
         if B == 0 or not sum(len(x) for x in o_idx):
             bi, cl, bb = (torch.zeros((0,), dtype=torch.long), torch.zeros((0, 1), dtype=batch["cls"].dtype),
                           torch.zeros((0, 4), dtype=torch.float32))
@@ -337,23 +411,29 @@ class BatchAugment:
             bi = torch.from_numpy(np.concatenate(o_idx)).long()
             cl = torch.from_numpy(np.concatenate(o_cls)).to(batch["cls"].dtype).reshape(-1, 1)
             bb = torch.from_numpy(np.concatenate(o_box)).float().clamp_(0.0, 1.0)
-        return table, bi, cl, bb, max_gt_count(bi)
+        return table, bi, cl, bb, max_gt_count(bi), partner, mix
 
     def __call__(self, batch: dict, device, epoch: int, step: int) -> dict:
         from .crater import prepare_batch
         if "img_u8" not in batch or self.hyp.is_off() or batch["img_meta"].shape[0] == 0:
             return prepare_batch(batch, device)              # synthetic batches carry no raw images
-        table, bi, cl, bb, max_gt = self.plan(batch, epoch, step)
+        table, bi, cl, bb, max_gt, partner, mix = self.plan_mix(batch, epoch, step)
         B, ch = int(batch["img_meta"].shape[0]), int(batch.get("img_ch", 1))
         colour = self.colours(B, epoch, step) if ch == 3 else None
-        tb = table_bytes(table)
-        n_table = tb.numel()                                    # B * 432: the colour table behind it is 8-byte aligned
-        if colour is not None:
-            tb = torch.cat((tb, table_bytes(colour)))           # one buffer, one transfer
+        # one buffer, one transfer: the primary table (B * 432 bytes), then for a batch with a mixed image the partner
+        # table (432 each) and the mix records (8 each), then the colour table (8 each): every offset is 8-byte aligned
+        parts = [table_bytes(t) for t in (table, partner, mix, colour) if t is not None]
+        cuts = np.cumsum([0] + [t.numel() for t in parts]).tolist()
+        tb = torch.cat(parts) if len(parts) > 1 else parts[0]
         if torch.device(device).type == "cuda":
             tb = tb.pin_memory()
         mv = lambda t: t.to(device, non_blocking=True)          # noqa: E731
         tb = mv(tb)
-        img = augment_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), tb[:n_table], int(batch["img_size"]), ch,
-                            tb[n_table:] if colour is not None else None)
+        views = [tb[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
+        col = views[-1] if colour is not None else None
+        if mix is None:
+            img = augment_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), views[0], int(batch["img_size"]), ch, col)
+        else:
+            img = augment_mix_batch(mv(batch["img_u8"]), mv(batch["img_meta"]), views[0], views[1], views[2],
+                                    int(batch["img_size"]), ch, col)
         return {"max_gt": max_gt, "img": img, "batch_idx": mv(bi), "cls": mv(cl), "bboxes": mv(bb)}

@@ -444,7 +444,9 @@ def build_parser():
                     "--augment on 3-plane data only")
     ap.add_argument("--hsv-s", type=float, default=0.7, help="saturation factor range (+/- fraction around 1); used "
                     "with --augment on 3-plane data only")
-    ap.add_argument("--close-mosaic", type=int, default=10, help="no mosaic in the last N epochs")
+    ap.add_argument("--mixup", type=float, default=0.0, help="probability that an image is blended with a second "
+                    "mosaic + affine sample of its batch (MixUp, ratio ~ Beta(32, 32)); used with --augment")
+    ap.add_argument("--close-mosaic", type=int, default=10, help="no mosaic and no MixUp in the last N epochs")
     ap.add_argument("--aug-seed", type=int, default=0)
     ap.add_argument("--val-per-class", action="store_true",
                     help="class-aware validation metrics: per-class AP, mAP over the classes with GT")
@@ -538,7 +540,8 @@ def main():
         from datasets import AugmentHyp, BatchAugment
         hyp = AugmentHyp(mosaic=args.mosaic, degrees=args.degrees, translate=args.translate, scale=args.aug_scale,
                          shear=args.shear, fliplr=args.fliplr, flipud=args.flipud, gain=args.gain,
-                         hsv_h=args.hsv_h if args.ch == 3 else 0.0, hsv_s=args.hsv_s if args.ch == 3 else 0.0)
+                         hsv_h=args.hsv_h if args.ch == 3 else 0.0, hsv_s=args.hsv_s if args.ch == 3 else 0.0,
+                         mixup=args.mixup)
         # train_one_epoch counts epochs from 1: the last `close_mosaic` of them draw no mosaic
         augment = BatchAugment(hyp, seed=args.aug_seed, rank=dp_ctx.rank if dp_ctx else 0,
                                no_mosaic_from=args.epochs - args.close_mosaic + 1)

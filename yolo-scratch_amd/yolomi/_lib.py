@@ -72,6 +72,14 @@ class AugColour(ctypes.Structure):
     _fields_ = [("hue", I32), ("sat", I32)]
 
 
+class AugMix(ctypes.Structure):
+    """ym_aug_mix (include/yolomi.h): Q16 weight of the primary image and the index of its partner entry."""
+    _fields_ = [("ratio", I32), ("partner", I32)]
+
+
+assert ctypes.sizeof(AugMix) == 8
+
+
 class LbEntry(ctypes.Structure):
     """ym_lb_entry (include/yolomi.h): per-image letterbox geometry, computed on the host."""
     _fields_ = [("nw", I32), ("nh", I32), ("left", I32), ("top", I32), ("w0", I32), ("h0", I32), ("sx", F32),
@@ -198,6 +206,7 @@ SIGNATURES = {
     "ym_augment_u8": (R, [P, P, P, INT, INT, P, P]),
     "ym_resize_linear_u8c": (R, [P, P, INT, INT, INT, P, P]),
     "ym_augment_u8c": (R, [P, P, P, P, INT, INT, INT, P, P]),
+    "ym_augment_mix_u8c": (R, [P, P, P, P, INT, P, P, INT, INT, INT, P, P]),
     "ym_letterbox_u8c": (R, [P, P, P, INT, INT, INT, INT, INT, P, P]),
     "ym_unletterbox_boxes": (R, [P, P, P, I64, I64, INT, INT, P, P]),
     "ym_slice_letterbox_u8c": (R, [P, P, INT, P, INT, INT, INT, INT, INT, P, P]),
