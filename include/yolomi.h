@@ -212,7 +212,12 @@ int ym_conv_kernel(const ym_conv_desc* d, int dir, char* name, int name_len);
  * (out_f32 = 2). */
 int ym_conv_fwd(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, const float* bias,
                 float* stat_sum, float* stat_sq, void* stream);
-/* dx (+)= conv_transpose(dz, w) using the [cin][kh][kw][cout] weight copy. */
+/* dx (+)= conv_transpose(dz, w) using the [cin][kh][kw][cout] weight copy.  d is the FORWARD descriptor: dz is the
+ * (n, oh, ow, cout) bf16 tensor in the y view (cout, y_ld, y_bs multiples of 8, a 16-byte aligned pointer), dx the
+ * (n, h, w, cin) bf16 tensor in the x view (x_ld, x_bs multiples of 4 and an 8-byte aligned pointer suffice, and cin
+ * need not be a multiple of 8: nothing outside cin's channels is written).  k in 1..3 with any pad, stride 1 or 2;
+ * n = 0 writes nothing.  accumulate = 1 rounds once (bf16(dx + v)) or twice (bf16(dx + bf16(v))) depending on the
+ * kernel and the view's alignment. */
 int ym_conv_dgrad(const ym_conv_desc* d, const uint16_t* dz, const uint16_t* wt, uint16_t* dx, void* stream);
 /* Weight gradient dW (fp32 OIHW) = sum over output pixels of dz (x) x, overwriting dw_oihw or adding
  * into it (accumulate = 1).  The K (pixel) axis is split over workgroups; the fp32 partials go to

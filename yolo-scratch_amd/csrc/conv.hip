@@ -1518,8 +1518,10 @@ extern "C" int ym_conv_dgrad(const ym_conv_desc* d, const uint16_t* dz, const ui
     YM_CHECK_ARG(d->stride == 1 || d->stride == 2, "ym_conv_dgrad: stride %d unsupported (1, 2)", d->stride);
     GemmArgs a = gemm_args(d, 1);
     a.x = dz; a.w = wt; a.y = dx;
+    // 16-B stores of whole 8-channel runs: with cin % 8 == 4 the last run of a pixel would end in the next slice of dx's
+    // buffer, so such a cin takes the fragment epilogue
     a.ep_lds = int64_t(d->n) * d->x_bs * 2 < (int64_t(1) << 31) && d->x_ld % 8 == 0 && d->x_bs % 8 == 0 &&
-               reinterpret_cast<uintptr_t>(dx) % 16 == 0;     // 16-B stores of whole 8-channel runs
+               d->cin % 8 == 0 && reinterpret_cast<uintptr_t>(dx) % 16 == 0;
     if (a.M == 0) return YM_OK;
     YM_CHECK_ARG(a.M < (int64_t(1) << 31), "ym_conv_dgrad: too many pixels");
     YM_CHECK_ARG(offsets_fit(d->y_bs, int64_t(d->h / d->stride) * (d->w / d->stride)),

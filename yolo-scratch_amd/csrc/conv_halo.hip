@@ -459,7 +459,8 @@ int halo_launch(const HaloPlan& p, const ym_conv_desc* d, int dgrad, const uint1
     a.TH = p.TH; a.TW = p.TW; a.HWd = p.TW + 2; a.HP = (p.TH + 2) * (p.TW + 2);
     // 16-B epilogue stores of transposed pixel rows (round 2 through LDS: 64-ch 80x80 fwd 0.076 -> 0.070 ms, dgrad
     // 0.066 -> 0.058; round 4 in registers)
-    a.ep_lds = !bias && a.out_mode != 1 && a.y_ld % 8 == 0 && a.y_bs % 8 == 0 &&
+    // (whole 8-channel runs: a channel count of 8 j + 4 would store 4 channels past the view, so it stores fragments)
+    a.ep_lds = !bias && a.out_mode != 1 && a.y_ld % 8 == 0 && a.y_bs % 8 == 0 && a.Nout % 8 == 0 &&
                int64_t(d->n) * a.y_bs * 2 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(y) % 16 == 0;
     a.RT = p.RT; a.CT = p.CT; a.ntiles = p.ntiles;
     if (!dgrad && st_sum) a.fold = bn_fold_args(fold);
