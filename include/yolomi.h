@@ -645,6 +645,30 @@ int ym_decode_nms_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int6
                         float conf, float iou_thr, float edge, int class_aware, int max_det, void* workspace,
                         size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
                         int64_t* out_labels, int64_t* out_index, int64_t* out_row, void* stream);
+/* Decode + greedy non-maximum MERGING over tiles: ym_decode_nms_tiles with a choice of match metric and
+ * with the kept box optionally grown to the union of what it absorbed.  Candidates, their order, the layout of `pred`
+ * and every output of ym_decode_nms_tiles are as there.  The match value of head a and candidate b, fp32, every
+ * operation rounded, inter / a1 / a2 formed as the IoU of ym_iou_row forms them:
+ *   YM_MATCH_IOU   inter / ((a1 + a2) - inter + 1e-6f)
+ *   YM_MATCH_IOS   inter / (fminf(a1, a2) + 1e-6f)      intersection over the smaller box
+ * Greedy loop: the best candidate still alive becomes a head and is kept; every later alive candidate (of the head's
+ * label when class_aware) with !(value <= match_thr) against THE HEAD'S OWN BOX is absorbed (never against the growing
+ * union: greedy merging, not the transitive form); max_det > 0 (class_aware only) stops after that many heads.
+ * Per head: score, label, out_index, out_row are the head's; out_merged (G, R; may be NULL) the number of candidates
+ * it absorbed; out_boxes the head's box (merge == 0) or the coordinate-wise union of the head and everything it
+ * absorbed (merge != 0): min of the x1s and y1s, max of the x2s and y2s, corners taken as stored.
+ * metric = YM_MATCH_IOU, merge = 0: every output of ym_decode_nms_tiles, bit for bit.
+ * YM_ERR_ARG before any launch: whatever ym_decode_nms_tiles refuses, metric outside {0, 1}, a NaN match_thr.
+ * Workspace: ym_decode_nmm_tiles_workspace_size (callable without a GPU). */
+#define YM_MATCH_IOU 0
+#define YM_MATCH_IOS 1
+size_t ym_decode_nmm_tiles_workspace_size(int64_t G, int64_t R, int class_aware);
+int ym_decode_nmm_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride, int64_t tile_stride,
+                        int64_t col_stride, const ym_tile_entry* table_dev, const int64_t* tile_begin, int64_t G,
+                        float conf, float match_thr, int metric, int merge, float edge, int class_aware, int max_det,
+                        void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                        float* out_scores, int64_t* out_labels, int64_t* out_index, int64_t* out_row,
+                        int32_t* out_merged, void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail
  * clip_grad_norm_(params, max_norm) + AdamW.step() over every parameter (train_yolo11_cuda.py:58-62,

@@ -112,6 +112,36 @@ __device__ __forceinline__ float iou_ref(float4 a, float4 b) {
     return inter / (uni + 1e-6f);
 }
 
+// The match value of greedy merging (ym_decode_nmm_tiles).  YM_MATCH_IOU is iou_ref itself; YM_MATCH_IOS
+// divides the same `inter` by the smaller area: a box cut by a tile border matches its whole twin at ~1 whatever its
+// share of the whole.
+template <int METRIC>
+__device__ __forceinline__ float match_ref(float4 a, float4 b) {
+    if constexpr (METRIC == YM_MATCH_IOU) {
+        return iou_ref(a, b);
+    } else {
+        float x1 = fmaxf(a.x, b.x), y1 = fmaxf(a.y, b.y);
+        float x2 = fminf(a.z, b.z), y2 = fminf(a.w, b.w);
+        float iw = x2 - x1, ih = y2 - y1;
+        iw = iw < 0.0f ? 0.0f : iw;
+        ih = ih < 0.0f ? 0.0f : ih;
+        float inter = iw * ih;
+        float a1 = (a.z - a.x) * (a.w - a.y);
+        float a2 = (b.z - b.x) * (b.w - b.y);
+        return inter / (fminf(a1, a2) + 1e-6f);
+    }
+}
+
+// Order-preserving integer image of a float (unsigned compare = float compare; -0 sorts below +0) and its inverse:
+// what the union pass of the MERGE instances takes integer min / max atomics on
+__device__ __forceinline__ uint32_t ord_bits(float s) {
+    uint32_t u = __float_as_uint(s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord_float(uint32_t o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
 __device__ __forceinline__ uint32_t desc_bits(float s) {
     uint32_t u = __float_as_uint(s);
     uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // ascending-order bits
@@ -242,12 +272,21 @@ __device__ void bitonic(uint64_t* keys, int P) {
 // ---------------------------------------------------------------- stage 2
 // CLS: class-aware suppression (a candidate is tested against heads of its own label only; labs[row] of type LT is
 // the label compared, equality only) and the max_det cap (0: none).  The CLS = false instances ignore both.
-template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t>
+//
+// Greedy merging (ym_decode_nmm_tiles; launched at clamp_norm = 0, so the union is taken over the boxes as
+// stored).  METRIC: the match value (match_ref).  MERGE: every absorbed candidate remembers the kept slot of the head
+// that absorbed it (slot[] beside alive[] in the register form, the galive word in the large-K form); after the loop
+// one parallel pass counts them into out_merged (may be null) and, with do_union, folds their boxes into the head's
+// out_boxes row by integer min / max atomics on ord_bits images.  Nothing is reduced inside the serial loop, and min,
+// max and integer adds do not depend on the order in which lanes arrive.  The METRIC = IoU, MERGE = false instances
+// are the suppression kernels of before, instruction for instruction.
+template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t, int METRIC = YM_MATCH_IOU, bool MERGE = false>
 __global__ void __launch_bounds__(NMS_THREADS)
 nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h, int clamp_norm, Ws w,
                  int32_t* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                  int64_t* __restrict__ out_labels, int64_t* __restrict__ out_index,
-                 const LT* __restrict__ labs = nullptr, int max_det = 0) {
+                 const LT* __restrict__ labs = nullptr, int max_det = 0, int32_t* __restrict__ out_merged = nullptr,
+                 int do_union = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* skeys = reinterpret_cast<uint64_t*>(smem);            // SORT_LDS_KEYS
     __shared__ int sh[NMS_WAVES + 1];
@@ -307,12 +346,14 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
     float4 mybox[REG_ITEMS];
     LT mylab[REG_ITEMS];
     bool alive[REG_ITEMS];
+    [[maybe_unused]] int slot[REG_ITEMS];     // MERGE: the kept slot that absorbed the candidate, -1: none
     const bool in_regs = K <= REG_ITEMS * NMS_THREADS;
     if (in_regs) {
 #pragma unroll
         for (int it = 0; it < REG_ITEMS; ++it) {
             int s = tid + it * NMS_THREADS;
             alive[it] = s < K;
+            if constexpr (MERGE) slot[it] = -1;
             if constexpr (CLS) {          // the CLS loop evaluates whole waves: no indeterminate operand
                 mybox[it] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 mylab[it] = LT(0);
@@ -325,6 +366,7 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
         }
     }
     // alive flags for the large-K path live in out_index scratch as bytes: reuse w.flag (now free)
+    // (MERGE: 1 alive, -(k + 1) absorbed by kept slot k)
     int32_t* galive = w.flag + base;
     if (!in_regs) {
         for (int s = tid; s < K; s += NMS_THREADS) galive[s] = 1;
@@ -372,32 +414,38 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
                     const bool live = alive[it] && s > head;
                     const bool test = live && mylab[it] == hl;
                     bool sup = false;
-                    if (__builtin_amdgcn_ballot_w64(test) != 0) sup = test && !(iou_ref(hb, mybox[it]) <= iou_thr);
+                    if (__builtin_amdgcn_ballot_w64(test) != 0) {
+                        sup = test && !(match_ref<METRIC>(hb, mybox[it]) <= iou_thr);
+                        if constexpr (MERGE) slot[it] = sup ? nkept - 1 : slot[it];   // (only where a lane was tested)
+                    }
                     alive[it] = live && !sup;
                     if (alive[it]) next = min(next, s);
                 } else if (alive[it] && s > head) {
-                    float v = iou_ref(hb, mybox[it]);
-                    if (!(v <= iou_thr)) alive[it] = false;     // reference keeps IoU <= thr (:396)
-                    else next = min(next, s);
+                    float v = match_ref<METRIC>(hb, mybox[it]);
+                    if (!(v <= iou_thr)) {                      // reference keeps IoU <= thr (:396)
+                        alive[it] = false;
+                        if constexpr (MERGE) slot[it] = nkept - 1;
+                    } else next = min(next, s);
                 } else if (s <= head) {
                     alive[it] = false;
                 }
             }
         } else {
             for (int s = tid; s < K; s += NMS_THREADS) {
-                if (s > head && galive[s]) {
+                if (s > head && (MERGE ? galive[s] > 0 : galive[s] != 0)) {
                     int f = int(uint32_t(keys[s]));
+                    const int32_t dead = MERGE ? -nkept : 0;
                     if constexpr (CLS) {
                         const int64_t row = base + w.frow[base + f];
                         // the label first: a candidate of another label loads no box and computes no IoU.  (Loading
                         // the box beside the label, unconditionally, saves one dependent load where the labels
                         // match and was 7 % faster with one class, but 1.3x slower with 5 classes and 2.1x with 80:
                         // DESIGN §18.)
-                        if (labs[row] == hl && !(iou_ref(hb, w.box[row]) <= iou_thr)) galive[s] = 0;
+                        if (labs[row] == hl && !(match_ref<METRIC>(hb, w.box[row]) <= iou_thr)) galive[s] = dead;
                         else next = min(next, s);
                     } else {
-                        float v = iou_ref(hb, w.box[base + w.frow[base + f]]);
-                        if (!(v <= iou_thr)) galive[s] = 0;
+                        float v = match_ref<METRIC>(hb, w.box[base + w.frow[base + f]]);
+                        if (!(v <= iou_thr)) galive[s] = dead;
                         else next = min(next, s);
                     }
                 }
@@ -421,12 +469,58 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
             bx.w = fminf(fmaxf(bx.w / img_h, 0.0f), 1.0f);
         }
         int64_t o = base + k;
-        reinterpret_cast<float4*>(out_boxes)[o] = bx;
+        if (MERGE && do_union)                  // the union pass works on the order-preserving integer images
+            reinterpret_cast<uint4*>(out_boxes)[o] = make_uint4(ord_bits(bx.x), ord_bits(bx.y), ord_bits(bx.z),
+                                                                ord_bits(bx.w));
+        else
+            reinterpret_cast<float4*>(out_boxes)[o] = bx;
         out_scores[o] = w.score[row];
         out_labels[o] = w.label[row];
         out_index[o] = f;
+        if constexpr (MERGE)
+            if (out_merged) out_merged[o] = 0;
     }
     if (tid == 0) out_count[b] = nk;
+
+    // e. MERGE: every absorbed candidate adds one to its head's count and folds its box into its head's row.  The rows
+    // were written above by other threads of this workgroup: the barrier orders those stores (the vector cache writes
+    // through) before the atomics, which run in L2, and the rows are read back by agent-scope atomic loads, never
+    // through this CU's vector cache.  A coordinate that cannot move
+    // its head's (min and max are monotone: the test may use a stale value safely) costs a load, not an atomic.
+    if constexpr (MERGE) {
+        if (!do_union && !out_merged) return;
+        __syncthreads();
+        uint32_t* ub = reinterpret_cast<uint32_t*>(out_boxes) + base * 4;
+        auto cur = [&](const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+        auto fold = [&](int k, float4 bx) {      // 0 <= k < nk: the slot of a kept head
+            if (out_merged) atomicAdd(&out_merged[base + k], 1);
+            if (do_union) {
+                uint32_t* u = ub + 4 * int64_t(k);
+                const uint32_t x1 = ord_bits(bx.x), y1 = ord_bits(bx.y), x2 = ord_bits(bx.z), y2 = ord_bits(bx.w);
+                if (x1 < cur(u + 0)) atomicMin(u + 0, x1);
+                if (y1 < cur(u + 1)) atomicMin(u + 1, y1);
+                if (x2 > cur(u + 2)) atomicMax(u + 2, x2);
+                if (y2 > cur(u + 3)) atomicMax(u + 3, y2);
+            }
+        };
+        if (in_regs) {
+#pragma unroll
+            for (int it = 0; it < REG_ITEMS; ++it)
+                if (slot[it] >= 0) fold(slot[it], mybox[it]);
+        } else {
+            for (int s = tid; s < K; s += NMS_THREADS) {
+                const int32_t g = galive[s];
+                if (g < 0) fold(-g - 1, w.box[base + w.frow[base + int(uint32_t(keys[s]))]]);
+            }
+        }
+        if (!do_union) return;
+        __syncthreads();
+        for (int k = tid; k < nk; k += NMS_THREADS) {
+            const uint32_t* u = ub + 4 * int64_t(k);
+            reinterpret_cast<float4*>(out_boxes)[base + k] =
+                make_float4(ord_float(cur(u + 0)), ord_float(cur(u + 1)), ord_float(cur(u + 2)), ord_float(cur(u + 3)));
+        }
+    }
 }
 
 // Sort of the filtered candidates (bitmask path) by rank: the keys (score descending, filtered
@@ -1035,6 +1129,101 @@ __global__ void tile_rows_kernel(int64_t R, Ws w, const int32_t* __restrict__ co
         out_row[base + k] = w.frow[base + index[base + k]];
 }
 
+// the greedy-merging instances of the image kernel; track: out_merged or the union is wanted
+template <bool CLS, int METRIC>
+void launch_nmm_instance(bool track, int64_t G, int64_t R, float match_thr, Ws w, int32_t* out_count, float* out_boxes,
+                         float* out_scores, int64_t* out_labels, int64_t* out_index, int max_det, int32_t* out_merged,
+                         int do_union, hipStream_t st) {
+    const size_t lds = size_t(SORT_LDS_KEYS) * sizeof(uint64_t);
+    const int64_t KP = pow2_at_least(R);
+    const int32_t* labs = CLS ? static_cast<const int32_t*>(w.label) : nullptr;
+    // (IoU without tracking is nms_image_kernel, which the caller launches: no instance of its own)
+    if (track || METRIC == YM_MATCH_IOU)
+        hipLaunchKernelGGL((nms_image_kernel<false, CLS, int32_t, METRIC, true>), dim3(unsigned(G)), dim3(NMS_THREADS),
+                           lds, st, R, KP, match_thr, 1.0f, 1.0f, 0, w, out_count, out_boxes, out_scores, out_labels,
+                           out_index, labs, max_det, out_merged, do_union);
+    else if constexpr (METRIC != YM_MATCH_IOU)
+        hipLaunchKernelGGL((nms_image_kernel<false, CLS, int32_t, METRIC, false>), dim3(unsigned(G)),
+                           dim3(NMS_THREADS), lds, st, R, KP, match_thr, 1.0f, 1.0f, 0, w, out_count, out_boxes,
+                           out_scores, out_labels, out_index, labs, max_det, static_cast<int32_t*>(nullptr), 0);
+}
+
+// nmm: ym_decode_nmm_tiles (fn names the entry point in messages); otherwise metric = IoU, merge = 0, out_merged null
+int decode_tiles_impl(const char* fn, bool nmm, const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
+                      int64_t tile_stride, int64_t col_stride, const ym_tile_entry* table_dev,
+                      const int64_t* tile_begin, int64_t G, float conf, float thr, int metric, int merge, float edge,
+                      int class_aware, int max_det, void* workspace, size_t workspace_bytes, int32_t* out_count,
+                      float* out_boxes, float* out_scores, int64_t* out_labels, int64_t* out_index, int64_t* out_row,
+                      int32_t* out_merged, void* stream) {
+    YM_CHECK_ARG(G >= 0 && G <= 65535 * int64_t(TILE_SPAN), "%s: G=%lld", fn, (long long)G);
+    YM_CHECK_ARG(max_det >= 0, "%s: max_det %d < 0", fn, max_det);
+    YM_CHECK_ARG(max_det == 0 || class_aware, "%s: max_det needs class_aware", fn);
+    YM_CHECK_ARG(edge == edge, "%s: edge is NaN", fn);
+    YM_CHECK_ARG(metric == YM_MATCH_IOU || metric == YM_MATCH_IOS, "%s: metric %d is neither YM_MATCH_IOU nor YM_MATCH_IOS",
+                 fn, metric);
+    YM_CHECK_ARG(!nmm || thr == thr, "%s: match_thr is NaN", fn);
+    YM_CHECK_ARG(T >= 0 && T <= INT32_MAX && N >= 0 && N < (int64_t(1) << 30) && C >= 1,
+                 "%s: bad shape T=%lld N=%lld C=%lld", fn, (long long)T, (long long)N, (long long)C);
+    YM_CHECK_ARG(col_stride >= 1 && (col_stride > 1 || row_stride >= 4 + C), "%s: row_stride < 4+C", fn);
+    YM_CHECK_ARG(tile_begin && tile_begin[0] >= 0, "%s: tile_begin", fn);
+    int64_t most = 0;
+    for (int64_t g = 0; g < G; ++g) {
+        YM_CHECK_ARG(tile_begin[g + 1] >= tile_begin[g], "%s: tile_begin is not monotone at %lld", fn, (long long)g);
+        most = std::max(most, tile_begin[g + 1] - tile_begin[g]);
+    }
+    YM_CHECK_ARG(tile_begin[G] <= T, "%s: tile_begin[G]=%lld > T=%lld", fn, (long long)tile_begin[G], (long long)T);
+    const int64_t R = N * most;                              // < 2^61: both factors were bounded above
+    YM_CHECK_ARG(R < (int64_t(1) << 30), "%s: R=%lld too large", fn, (long long)R);
+    if (G == 0) return YM_OK;
+    YM_CHECK_ARG(out_count, "%s: out_count is NULL", fn);
+    hipStream_t st = as_stream(stream);
+    if (R == 0) return hipMemsetAsync(out_count, 0, G * sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
+    YM_CHECK_ARG(pred && table_dev && workspace && out_boxes && out_scores && out_labels && out_index,
+                 "%s: NULL argument", fn);
+    const size_t need = tiles_ws_bytes(G, R);
+    YM_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need);
+    Ws w = carve_tiles(workspace, G, R);
+    for (int64_t g0 = 0; g0 < G; g0 += TILE_SPAN) {
+        const int ng = int(std::min<int64_t>(TILE_SPAN, G - g0));
+        TileSpan span = {};
+        for (int k = 0; k <= ng; ++k) span.begin[k] = int32_t(tile_begin[g0 + k]);
+        if (C <= 64)
+            hipLaunchKernelGGL(rowmax_tiles_thread_kernel, dim3(unsigned((R + 255) / 256), unsigned(ng)), dim3(256), 0,
+                               st, pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge,
+                               w);
+        else
+            hipLaunchKernelGGL(rowmax_tiles_wave_kernel, dim3(unsigned((R + 3) / 4), unsigned(ng)), dim3(256), 0, st,
+                               pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge, w);
+    }
+    YM_LAUNCH_CHECK("rowmax tiles");
+    const bool track = merge != 0 || out_merged != nullptr;
+    if (metric == YM_MATCH_IOU && !track) {                  // the suppression kernels themselves
+        const int rc = launch_nms(G, R, thr, 1.0f, 1.0f, 0, w, out_count, out_boxes, out_scores, out_labels, out_index,
+                                  st, class_aware != 0, max_det);
+        if (rc != YM_OK) return rc;
+    } else {
+        const int du = merge != 0;
+        if (class_aware && metric == YM_MATCH_IOS)
+            launch_nmm_instance<true, YM_MATCH_IOS>(track, G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                    out_index, max_det, out_merged, du, st);
+        else if (class_aware)
+            launch_nmm_instance<true, YM_MATCH_IOU>(track, G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                    out_index, max_det, out_merged, du, st);
+        else if (metric == YM_MATCH_IOS)
+            launch_nmm_instance<false, YM_MATCH_IOS>(track, G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                     out_index, 0, out_merged, du, st);
+        else
+            launch_nmm_instance<false, YM_MATCH_IOU>(track, G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                     out_index, 0, out_merged, du, st);
+        YM_LAUNCH_CHECK("nms_image_kernel (merging)");
+    }
+    if (!out_row) return YM_OK;
+    hipLaunchKernelGGL(tile_rows_kernel, dim3(unsigned(std::min<int64_t>((R + 255) / 256, 64)), unsigned(G)),
+                       dim3(256), 0, st, R, w, out_count, out_index, out_row);
+    YM_LAUNCH_CHECK("tile_rows_kernel");
+    return YM_OK;
+}
+
 }  // namespace
 }  // namespace ym
 
@@ -1050,51 +1239,26 @@ extern "C" int ym_decode_nms_tiles(const float* pred, int64_t T, int64_t N, int6
                                    int class_aware, int max_det, void* workspace, size_t workspace_bytes,
                                    int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels,
                                    int64_t* out_index, int64_t* out_row, void* stream) {
-    YM_CHECK_ARG(G >= 0 && G <= 65535 * int64_t(TILE_SPAN), "ym_decode_nms_tiles: G=%lld", (long long)G);
-    YM_CHECK_ARG(max_det >= 0, "ym_decode_nms_tiles: max_det %d < 0", max_det);
-    YM_CHECK_ARG(max_det == 0 || class_aware, "ym_decode_nms_tiles: max_det needs class_aware");
-    YM_CHECK_ARG(edge == edge, "ym_decode_nms_tiles: edge is NaN");
-    YM_CHECK_ARG(T >= 0 && T <= INT32_MAX && N >= 0 && N < (int64_t(1) << 30) && C >= 1,
-                 "ym_decode_nms_tiles: bad shape T=%lld N=%lld C=%lld", (long long)T, (long long)N, (long long)C);
-    YM_CHECK_ARG(col_stride >= 1 && (col_stride > 1 || row_stride >= 4 + C), "ym_decode_nms_tiles: row_stride < 4+C");
-    YM_CHECK_ARG(tile_begin && tile_begin[0] >= 0, "ym_decode_nms_tiles: tile_begin");
-    int64_t most = 0;
-    for (int64_t g = 0; g < G; ++g) {
-        YM_CHECK_ARG(tile_begin[g + 1] >= tile_begin[g], "ym_decode_nms_tiles: tile_begin is not monotone at %lld",
-                     (long long)g);
-        most = std::max(most, tile_begin[g + 1] - tile_begin[g]);
-    }
-    YM_CHECK_ARG(tile_begin[G] <= T, "ym_decode_nms_tiles: tile_begin[G]=%lld > T=%lld", (long long)tile_begin[G],
-                 (long long)T);
-    const int64_t R = N * most;                              // < 2^61: both factors were bounded above
-    YM_CHECK_ARG(R < (int64_t(1) << 30), "ym_decode_nms_tiles: R=%lld too large", (long long)R);
-    if (G == 0) return YM_OK;
-    YM_CHECK_ARG(out_count, "ym_decode_nms_tiles: out_count is NULL");
-    hipStream_t st = as_stream(stream);
-    if (R == 0) return hipMemsetAsync(out_count, 0, G * sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
-    YM_CHECK_ARG(pred && table_dev && workspace && out_boxes && out_scores && out_labels && out_index,
-                 "ym_decode_nms_tiles: NULL argument");
-    const size_t need = tiles_ws_bytes(G, R);
-    YM_CHECK_ARG(workspace_bytes >= need, "ym_decode_nms_tiles: workspace too small (%zu < %zu)", workspace_bytes, need);
-    Ws w = carve_tiles(workspace, G, R);
-    for (int64_t g0 = 0; g0 < G; g0 += TILE_SPAN) {
-        const int ng = int(std::min<int64_t>(TILE_SPAN, G - g0));
-        TileSpan span = {};
-        for (int k = 0; k <= ng; ++k) span.begin[k] = int32_t(tile_begin[g0 + k]);
-        if (C <= 64)
-            hipLaunchKernelGGL(rowmax_tiles_thread_kernel, dim3(unsigned((R + 255) / 256), unsigned(ng)), dim3(256), 0,
-                               st, pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge,
-                               w);
-        else
-            hipLaunchKernelGGL(rowmax_tiles_wave_kernel, dim3(unsigned((R + 3) / 4), unsigned(ng)), dim3(256), 0, st,
-                               pred, N, C, row_stride, tile_stride, col_stride, table_dev, span, g0, R, conf, edge, w);
-    }
-    YM_LAUNCH_CHECK("rowmax tiles");
-    const int rc = launch_nms(G, R, iou_thr, 1.0f, 1.0f, 0, w, out_count, out_boxes, out_scores, out_labels, out_index,
-                              st, class_aware != 0, max_det);
-    if (rc != YM_OK || !out_row) return rc;
-    hipLaunchKernelGGL(tile_rows_kernel, dim3(unsigned(std::min<int64_t>((R + 255) / 256, 64)), unsigned(G)),
-                       dim3(256), 0, st, R, w, out_count, out_index, out_row);
-    YM_LAUNCH_CHECK("tile_rows_kernel");
-    return YM_OK;
+    return decode_tiles_impl("ym_decode_nms_tiles", false, pred, T, N, C, row_stride, tile_stride, col_stride,
+                             table_dev, tile_begin, G, conf, iou_thr, YM_MATCH_IOU, 0, edge, class_aware, max_det,
+                             workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                             out_row, nullptr, stream);
+}
+
+// (the absorbing slots live in registers and in the flag words: ym_decode_nms_tiles's workspace)
+extern "C" size_t ym_decode_nmm_tiles_workspace_size(int64_t G, int64_t R, int class_aware) {
+    return ym_decode_nms_tiles_workspace_size(G, R, class_aware);
+}
+
+extern "C" int ym_decode_nmm_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
+                                   int64_t tile_stride, int64_t col_stride, const ym_tile_entry* table_dev,
+                                   const int64_t* tile_begin, int64_t G, float conf, float match_thr, int metric,
+                                   int merge, float edge, int class_aware, int max_det, void* workspace,
+                                   size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
+                                   int64_t* out_labels, int64_t* out_index, int64_t* out_row, int32_t* out_merged,
+                                   void* stream) {
+    return decode_tiles_impl("ym_decode_nmm_tiles", true, pred, T, N, C, row_stride, tile_stride, col_stride,
+                             table_dev, tile_begin, G, conf, match_thr, metric, merge, edge, class_aware, max_det,
+                             workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                             out_row, out_merged, stream);
 }

@@ -3,6 +3,8 @@
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --scale s --ch 3 --nc 80 --ema
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source video_frames/ --ch 3 --nc 80 --rect
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source orbital_frames/ --slice 640 --slice-edge 4
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source orbital_frames/ --slice 640 --slice-merge nmm \
+        --slice-metric ios
 
 Per image `<save-dir>/<stem>.txt` with rows `cls cx cy w h conf` normalised to the source image (the label format of
 datasets/yolo_txt.py plus the confidence), and one `<save-dir>/predictions.json` with the pixel boxes.  The images
@@ -51,6 +53,12 @@ def build_parser():
                     help="skip the extra pass over the whole image (it sees objects larger than a window)")
     ap.add_argument("--slice-edge", type=float, default=0.0,
                     help="drop a window's boxes within this many pixels of a window side inside the image (0: none)")
+    ap.add_argument("--slice-merge", type=str, default="nms", choices=["nms", "nmm"],
+                    help="how a sliced image's boxes are joined: nms suppresses what overlaps a kept box, nmm merges "
+                         "it into the kept box, which becomes the union (--iou is the match threshold)")
+    ap.add_argument("--slice-metric", type=str, default="iou", choices=["iou", "ios"],
+                    help="the overlap --iou is compared with: iou, or ios, the intersection over the smaller box, "
+                         "which joins a box cut by a window border to its whole twin")
     ap.add_argument("--save-dir", type=str, default="runs/predict")
     return ap
 
@@ -62,6 +70,8 @@ def parse_args(argv=None):
         ap.error("--slice is a window size in pixels")
     if args.slice and args.rect:
         ap.error("--slice and --rect exclude each other")
+    if (args.slice_merge, args.slice_metric) != ("nms", "iou") and not args.slice:
+        ap.error("--slice-merge and --slice-metric need --slice")
     return args
 
 
@@ -118,7 +128,8 @@ def main(argv=None):
     print(f"Loaded {key} from {args.weights}")
     predictor = Predictor(model, imgsz=args.imgsz, ch=args.ch, conf=args.conf, iou=args.iou, max_det=args.max_det,
                           class_aware=True, device=device, batch=args.batch, rect=args.rect, slice=args.slice,
-                          slice_overlap=args.slice_overlap, slice_full=args.slice_full, slice_edge=args.slice_edge)
+                          slice_overlap=args.slice_overlap, slice_full=args.slice_full, slice_edge=args.slice_edge,
+                          slice_merge=args.slice_merge, slice_metric=args.slice_metric)
     save_dir = Path(args.save_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     order = list(range(len(files)))

@@ -111,6 +111,25 @@ def decode_nms(pred: torch.Tensor, img_size, conf: float, iou_thr: float, class_
     return [{"boxes": boxes[b, :k], "scores": scores[b, :k], "labels": labels[b, :k]} for b, k in enumerate(counts)]
 
 
+METRICS = {"iou": 0, "ios": 1}                          # YM_MATCH_IOU, YM_MATCH_IOS
+
+
+def decode_nmm_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, conf: float, thr: float,
+                     metric: str = "iou", merge: bool = False, class_aware: bool = False, max_det: int = 0,
+                     edge: float = 0.0):
+    """Decode + greedy merging of sliced inference (ym_decode_nmm_tiles): decode_nms_tiles's candidates
+    and order; a kept box absorbs every later candidate (of its label when class_aware) whose match value with the
+    kept box itself exceeds `thr`.  `metric`: "iou", or "ios", the intersection over the smaller box, which matches a
+    box that a tile border cut with its whole twin.  `merge`: "boxes" holds the union of the kept box and what it
+    absorbed instead of the kept box.
+
+    Returns the dict of decode_nms_tiles plus "merged" (G, R) int32: how many candidates each kept box absorbed."""
+    if metric not in METRICS:
+        raise ValueError(f"decode_nmm_tiles: metric is 'iou' or 'ios', got {metric!r}")
+    return _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, edge,
+                         (METRICS[metric], int(bool(merge))))
+
+
 def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, conf: float, iou_thr: float,
                      class_aware: bool = False, max_det: int = 0, edge: float = 0.0):
     """Decode + NMS of sliced inference (ym_decode_nms_tiles): pred read as (T, N, 4+C), one slice per
@@ -122,6 +141,11 @@ def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, co
     Returns the padded dict of decode_nms(..., padded=True) with R = N * (the largest tile count) rows per image and
     "boxes" in source pixels (xyxy, unnormalised), plus "rows" (G, R) int64: the row of the image's (tile, row)
     concatenation a kept box came from, tile = row // N."""
+    return _decode_tiles(pred, table_dev, tile_begin, conf, iou_thr, class_aware, max_det, edge, None)
+
+
+def _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, edge, nmm):
+    """nmm: None (ym_decode_nms_tiles) or (metric, merge) (ym_decode_nmm_tiles, which also fills "merged")."""
     import ctypes
     from ._lib import TileEntry, lib
     require_device(pred, table_dev)
@@ -149,9 +173,16 @@ def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, co
     labels = torch.empty(G, R, dtype=torch.int64, device=dev)
     index = torch.empty(G, R, dtype=torch.int64, device=dev)
     rows = torch.empty(G, R, dtype=torch.int64, device=dev)
-    call("ym_decode_nms_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
-         float(conf), float(iou_thr), float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes, ptr(cnt),
-         ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), stream_ptr(dev))
-    counts = cnt.cpu().tolist()                      # the single host sync of the group
-    return {"boxes": boxes, "scores": scores, "labels": labels, "count": cnt, "counts": counts, "index": index,
-            "rows": rows}
+    out = {"boxes": boxes, "scores": scores, "labels": labels, "count": cnt, "index": index, "rows": rows}
+    if nmm is None:
+        call("ym_decode_nms_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
+             float(conf), float(thr), float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes, ptr(cnt),
+             ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), stream_ptr(dev))
+    else:
+        out["merged"] = torch.empty(G, R, dtype=torch.int32, device=dev)
+        call("ym_decode_nmm_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
+             float(conf), float(thr), nmm[0], nmm[1], float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes,
+             ptr(cnt), ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), ptr(out["merged"]),
+             stream_ptr(dev))
+    out["counts"] = cnt.cpu().tolist()               # the single host sync of the group
+    return out

@@ -16,6 +16,8 @@ results come back in input order.
 their overlapping TILE x TILE windows at full resolution (datasets.slicing), each letterboxed into the imgsz x imgsz
 frame by ym_slice_letterbox_u8c, `batch` tiles per forward; ym_decode_nms_tiles maps every tile's candidates into
 source pixels and runs one NMS per source image, so there is no unletterbox step.  One host sync per group.
+`slice_merge` / `slice_metric` put ym_decode_nmm_tiles in that NMS's place: greedy merging, matched by the
+IoU or by the intersection over the smaller box.
 """
 from __future__ import annotations
 
@@ -36,12 +38,17 @@ class Predictor:
     most-recently-used frames are kept (yolomi.graph.FrameLRU).  Without `rect` nothing is ever dropped.
     `slice`: sliced inference on slice x slice windows that share `slice_overlap` of their side; `slice_full`: one more
     pass over the whole image, for objects larger than a tile; `slice_edge` > 0: a tile's boxes within that many
-    pixels of a window side that is not an image side are left to the neighbouring tile.  Not with `rect`."""
+    pixels of a window side that is not an image side are left to the neighbouring tile.  Not with `rect`.
+    `slice_merge`: "nms" suppresses the tiles' boxes, "nmm" merges them greedily: a kept box absorbs what
+    matches it and becomes the union, and the results also carry "merged", the number each box absorbed;
+    `slice_metric`: the match value `iou` is compared with, "iou" or "ios" (intersection over the smaller box, which
+    joins a box cut by a tile border to its whole twin).  Both need `slice`."""
 
     def __init__(self, model, imgsz: int = 640, ch: int | None = None, conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114,
                  rect: bool = False, max_frames: int = 8, slice: int = 0, slice_overlap: float = 0.2,
-                 slice_full: bool = True, slice_edge: float = 0.0):
+                 slice_full: bool = True, slice_edge: float = 0.0, slice_merge: str = "nms",
+                 slice_metric: str = "iou"):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise YolomiError("Predictor runs on the MI355X only (no CPU fallback)")
@@ -59,6 +66,12 @@ class Predictor:
         self.slice_full, self.slice_edge = bool(slice_full), float(slice_edge)
         if self.slice < 0:
             raise ValueError("Predictor: slice is a tile size in pixels (0: off)")
+        if slice_merge not in ("nms", "nmm") or slice_metric not in _post.METRICS:
+            raise ValueError(f"Predictor: slice_merge is 'nms' or 'nmm' and slice_metric 'iou' or 'ios', got "
+                             f"{slice_merge!r}, {slice_metric!r}")
+        if (slice_merge, slice_metric) != ("nms", "iou") and not self.slice:
+            raise ValueError("Predictor: slice_merge and slice_metric belong to sliced inference (slice=TILE)")
+        self.slice_merge, self.slice_metric = slice_merge, slice_metric
         if self.slice:
             if rect:
                 raise ValueError("Predictor: slice and rect exclude each other (tiles run in the imgsz x imgsz frame)")
@@ -127,7 +140,9 @@ class Predictor:
         T = begin[-1]
         if T == 0:
             z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.device)    # noqa: E731
-            return [{"boxes": z(0, 4), "scores": z(0), "labels": z(0, dt=torch.int64)} for _ in images]
+            nmm = (self.slice_merge, self.slice_metric) != ("nms", "iou")
+            return [{"boxes": z(0, 4), "scores": z(0), "labels": z(0, dt=torch.int64),
+                     **({"merged": z(0, dt=torch.int32)} if nmm else {})} for _ in images]
         Tp = -(-T // nb) * nb
         mv = lambda t: t.to(self.device, non_blocking=True)          # noqa: E731
         tdev = mv(tile_bytes(table, T, Tp).pin_memory())
@@ -139,11 +154,15 @@ class Predictor:
             if ybuf is None:
                 ybuf = torch.empty(Tp, *y.shape[1:], dtype=y.dtype, device=y.device)
             ybuf[lo:lo + nb].copy_(y)                                # before the next replay overwrites it
-        d = _post.decode_nms_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou,
-                                   class_aware=self.class_aware, max_det=self.max_det if self.class_aware else 0,
-                                   edge=self.slice_edge)
-        return [{"boxes": d["boxes"][g, :k], "scores": d["scores"][g, :k], "labels": d["labels"][g, :k]}
-                for g, k in enumerate(d["counts"])]
+        kw = dict(class_aware=self.class_aware, max_det=self.max_det if self.class_aware else 0, edge=self.slice_edge)
+        keys = ("boxes", "scores", "labels")
+        if (self.slice_merge, self.slice_metric) == ("nms", "iou"):
+            d = _post.decode_nms_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou, **kw)
+        else:
+            d = _post.decode_nmm_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou,
+                                       metric=self.slice_metric, merge=self.slice_merge == "nmm", **kw)
+            keys += ("merged",)
+        return [{key: d[key][g, :k] for key in keys} for g, k in enumerate(d["counts"])]
 
     def frame_of(self, im):
         """(H, W) of one image's rectangular frame."""
