@@ -71,6 +71,30 @@ def test_attention_unsupported_head_dim_raises():
         mod(torch.randn(1, 256, 4, 4, device="cuda"))
 
 
+def test_block_second_backward_without_zero_grad_accumulates():
+    """Two forward + backward passes through one block plan without zero_grad(): each parameter's .grad is the sum
+    of the two gradients taken separately (as autograd accumulates, and as the whole-model and Detect plans do).
+    The sum is formed once in fp32, so the bound is this file's gradient tolerance."""
+    from models import Conv
+    torch.manual_seed(3)
+    mod = Conv(8, 16, 3).cuda().train()
+    xs = [torch.randn(2, 8, 16, 16, generator=torch.Generator().manual_seed(s)).cuda() for s in (11, 12)]
+    dys = [torch.randn(2, 16, 16, 16, generator=torch.Generator().manual_seed(s)).cuda() for s in (21, 22)]
+    state = {k: v.clone() for k, v in mod.state_dict().items()}
+    single = []
+    for x, dy in zip(xs, dys):
+        mod.load_state_dict(state)                  # the same running statistics for every pass
+        mod.zero_grad(set_to_none=True)
+        mod(x).backward(dy)
+        single.append({k: p.grad.clone() for k, p in mod.named_parameters()})
+    mod.load_state_dict(state)
+    mod.zero_grad(set_to_none=True)
+    for x, dy in zip(xs, dys):
+        mod(x).backward(dy)
+    for k, p in mod.named_parameters():
+        assert rel(p.grad, single[0][k] + single[1][k]) < 2e-2, k
+
+
 @pytest.mark.parametrize("name", ["dfl_arange", "dfl_kaiming"])
 def test_dfl_standalone_vs_reference(golden, name):
     from models import DFL

@@ -43,10 +43,8 @@ def main():
     cfg = yaml.safe_load((ROOT / "yolo-scratch_amd" / "configs" / "yolo11n_crater.yaml").read_text())
     cfg["scale"] = args.scale
     model = build_yolo11(cfg, ch=1, nc=5).train()
-    plan = G.Plan(model, args.batch, args.imgsz, args.imgsz, torch.device("cpu"), True)
-    plan.input_requires_grad = False
-    plan.is_model = True
-    G.lower_model(plan, model, (args.batch, args.imgsz, args.imgsz))
+    plan = G.lower_model(G.Plan(model, args.batch, args.imgsz, args.imgsz, torch.device("cpu"), True, "model"), model,
+                         (args.batch, args.imgsz, args.imgsz))
     ops = plan.ops
     idx = {id(op): i for i, op in enumerate(ops)}
     writers = []                     # (op index, gradient key) in backward order

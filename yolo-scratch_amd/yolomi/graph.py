@@ -129,12 +129,13 @@ class WeightStore:
         self.items = []          # (module_param, fwd tensor, t tensor, cout_t)
         self.table_dev = None
         self.key = None
+        self.total = 0           # elements of every master weight (the conversion launch's extent)
 
     def add(self, w: torch.nn.Parameter, need_t: bool, cout_t: int | None = None):
         co, ci, kh, kw = w.shape
         cout_t = cout_t or co
         # an eval-mode model plan never runs a backward: no transposed data-gradient copy to prepare
-        need_t = need_t and (self.plan.training or not getattr(self.plan, "is_model", False))
+        need_t = need_t and (self.plan.training or self.plan.kind != "model")
         fwd = torch.empty(co, kh, kw, ci, dtype=F16, device=self.plan.dev)
         t = torch.zeros(ci, kh, kw, cout_t, dtype=BF16, device=self.plan.dev) if need_t else None
         self.items.append((w, fwd, t, cout_t))
@@ -188,7 +189,7 @@ def _overlap(k1, k2):
 class ConvBN:
     """Conv2d (k in {1,3}, groups=1) -> BatchNorm2d -> SiLU|Identity (+ residual) — reference Conv :21-33."""
 
-    def __init__(self, plan, m, x: View, y: View, s=1, act=True, res: View | None = None):
+    def __init__(self, plan, m, x: View, y: View, s=1, act=True, res: View | None = None, out32=None):
         w = m.conv.weight
         self.m, self.x, self.y, self.res, self.act = m, x, y, res, int(act)
         co, ci, k, _ = w.shape
@@ -198,19 +199,30 @@ class ConvBN:
         assert (oh, ow) == (y.H, y.W), ((oh, ow), (y.H, y.W))
         B = plan.B
         self.M, self.HW = B * oh * ow, oh * ow
-        self.z = torch.empty(self.M, co, dtype=BF16, device=plan.dev)
-        self.wf, self.wt = plan.weights.add(w, need_t=x.act is not None)
+        self.wf, self.wt = plan.weights.add(w, need_t=True)
         d = ConvDesc()
         d.n, d.h, d.w, d.cin, d.oh, d.ow, d.cout = B, x.H, x.W, ci, oh, ow, co
         d.k, d.stride, d.pad = k, s, k // 2
         d.x_bs, d.x_ld, d.y_bs, d.y_ld = x.bs, x.ld, self.HW * co, co
         d.out_f32 = 2                                                   # fp16 pre-BN z
         self.desc = d
-        self.G = lib().ym_conv_fwd_stat_rows(ctypes.byref(d))
-        self.ps = torch.empty(2, max(self.G, lib().ym_bn_bwd_blocks(self.M, co)), co, dtype=F32, device=plan.dev)
-        self.bnv = torch.empty(4, co, dtype=F32, device=plan.dev)      # scale, shift, mean, rstd
-        self.coef = torch.empty(3, co, dtype=F32, device=plan.dev)
+        self._alloc(plan, lib().ym_conv_fwd_stat_rows(ctypes.byref(d)), out32)
         plan.need_wgrad_ws(d)
+
+    def _alloc(self, plan, G, out32=None):
+        """The BatchNorm state every Conv block keeps (M, co set): z, G rows of forward statistics (and the backward's
+        Gb), the BN vectors, the backward's apply coefficients, and the per-op caches, filled on first use."""
+        co, dev = self.co, plan.dev
+        self.G, self.Gb = G, lib().ym_bn_bwd_blocks(self.M, co)
+        self.z = torch.empty(self.M, co, dtype=BF16, device=dev)
+        self.ps = torch.empty(2, max(G, self.Gb), co, dtype=F32, device=dev)
+        self.bnv = torch.empty(4, co, dtype=F32, device=dev)       # scale, shift, mean, rstd
+        self.coef = torch.empty(3, co, dtype=F32, device=dev)
+        self.out32 = out32        # fp32 tensor the BatchNorm apply also writes y to (SPPF's cv1: the pools' input)
+        self._sa = self._sc = None                  # static launch arguments (_static_args, forward)
+        self._fused_c = self._bwd_fold = None       # the library's answers: ym_conv_fwd_bn_fused, ym_bn_bwd_fold_ok
+        self._fold_s = self._evf = None             # (key, value): _fold, _eval_one_launch
+        self._evws = self._ws = None                # eval K-split and backward scratch
 
     def flops(self):
         return 2 * self.M * self.co * self.ci * self.k * self.k
@@ -248,14 +260,14 @@ class ConvBN:
         own buffers), converted once: at bs1 the eval forward is host-bound and re-deriving them per
         launch (tensor indexing, view offsets) was about half of its ~20 us of host time per conv block.
         Parameters stay looked up per call (a replaced nn.Parameter is seen)."""
-        a = self.__dict__.get("_sa")
+        a = self._sa
         if a is None:
             r = self.res
             bnv = tuple(self.bnv[i].data_ptr() for i in range(4))
             ss, sq = self.ps[0].data_ptr(), self.ps[1].data_ptr()
             apply = (self.z.data_ptr(), self.M, self.co, self.HW, bnv[0], bnv[1], self.act,
                      r.ptr() if r else None, r.bs if r else 0, r.ld if r else 0, self.y.ptr(), self.y.bs, self.y.ld,
-                     _p(getattr(self, "out32", None)))
+                     _p(self.out32))
             a = self._sa = (bnv, ss, sq, apply)
         return a
 
@@ -264,7 +276,7 @@ class ConvBN:
         launch's tail (the pipelined forward; YM_FOLD=0: conv, then ym_bn_finalize, as for the other kernels)."""
         if os.environ.get("YM_FOLD", "1") == "0":
             return False
-        f = self.__dict__.get("_fused_c")
+        f = self._fused_c
         if f is None:
             f = self._fused_c = bool(lib().ym_conv_fwd_bn_fused(ctypes.byref(self.desc)))
         return f
@@ -276,7 +288,7 @@ class ConvBN:
         (sc, sh, mu, rs), _, _, _ = self._static_args(plan)
         key = (_p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked),
                plan.bn_ws.data_ptr(), float(bn.momentum), float(bn.eps))
-        f = self.__dict__.get("_fold_s")
+        f = self._fold_s
         if f is None or f[0] != key:
             fs = BnFold(gamma=key[0], beta=key[1], running_mean=key[2], running_var=key[3],
                         num_batches_tracked=key[4], scale=sc, shift=sh, mean=mu, rstd=rs, workspace=key[5],
@@ -301,11 +313,27 @@ class ConvBN:
                 call("ym_bn_finalize", ssp, sqp, self.G, self.co, float(self.M), _p(bn.weight),
                      _p(bn.bias), _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked),
                      float(bn.momentum), float(bn.eps), sc, sh, mu, rs, plan.bn_ws.data_ptr(), st)
-            elif not plan.eval_coeff_batched:
-                call("ym_bn_eval_coeff", self.co, _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
-                     _p(bn.running_var), float(bn.eps), sc, sh, st)
+            else:
+                self._eval_coeff(plan, st)
             call("ym_bn_apply", *apply, st)
         self._timed(plan, "bn", plan._cur_stream, run, work)
+
+    def _eval_coeff(self, plan, st):
+        """Eval: this layer's BatchNorm scale / shift from its running statistics, unless the plan forms every layer's
+        in one launch before the ops run (Plan._eval_coeffs)."""
+        if plan.eval_coeff_batched:
+            return
+        bn = self.m.bn
+        (sc, sh, _, _), _, _, _ = self._static_args(plan)
+        call("ym_bn_eval_coeff", self.co, _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var),
+             float(bn.eps), sc, sh, st)
+
+    def _eval_aligned(self, y_ld=8):
+        """Whether the views suit the one-launch eval kernels' vector accesses: y at 16 bytes with rows of a multiple of
+        y_ld channels, the residual at 8 bytes with rows of a multiple of 4 (a view's batch stride is a multiple of its
+        row)."""
+        y, r = self.y, self.res
+        return y.ptr() % 16 == 0 and y.ld % y_ld == 0 and (r is None or (r.ptr() % 8 == 0 and r.ld % 4 == 0))
 
     def _eval_one_launch(self, plan):
         """ym_conv_fwd_eval arguments for this op's eval forward (conv + eval BatchNorm + SiLU + residual in one
@@ -313,12 +341,12 @@ class ConvBN:
         fp32 copy.  YM_EVAL_FUSE=0 opts out."""
         # keyed on the library's policy generation too: ym_conv_fwd_eval_ok and the K-split workspace are answers of the
         # selection policies in force (yolomi_experimental.h), re-asked after any setter call
-        on = (os.environ.get("YM_EVAL_FUSE", "1") != "0" and "out32" not in self.__dict__, lib().ym_policy_generation())
-        f = self.__dict__.get("_evf")
+        on = (os.environ.get("YM_EVAL_FUSE", "1") != "0" and self.out32 is None, lib().ym_policy_generation())
+        f = self._evf
         if f is None or f[0] != on:
             args = None
             r = self.res
-            if on[0] and (r is None or (r.ptr() % 8 == 0 and r.ld % 4 == 0)) and self.y.ptr() % 16 == 0:
+            if on[0] and self._eval_aligned(y_ld=1):      # the output's row stride is ym_conv_fwd_eval_ok's to judge
                 d = ConvDesc.from_buffer_copy(self.desc)
                 d.y_bs, d.y_ld, d.out_f32, d.accumulate = self.y.bs, self.y.ld, 2, 0
                 if lib().ym_conv_fwd_eval_ok(ctypes.byref(d)):
@@ -337,15 +365,11 @@ class ConvBN:
         if not plan.training:
             ev = self._eval_one_launch(plan)
             if ev is not None:
-                bn = self.m.bn
-                if not plan.eval_coeff_batched:
-                    sc, sh = ev[4], ev[5]
-                    call("ym_bn_eval_coeff", self.co, _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
-                         _p(bn.running_var), float(bn.eps), sc, sh, st)
+                self._eval_coeff(plan, st)
                 self._timed(plan, "fwd", plan._cur_stream, lambda: call("ym_conv_fwd_eval", *ev[1:], st))
                 return
         ss, sq = self.ps[0], self.ps[1]
-        conv = self.__dict__.get("_sc")
+        conv = self._sc
         if conv is None:
             conv = self._sc = (ctypes.byref(self.desc), self.x.ptr(), self.wf.data_ptr(), self.z.data_ptr(), None,
                                ss.data_ptr() if plan.training else None, sq.data_ptr() if plan.training else None)
@@ -358,36 +382,39 @@ class ConvBN:
         self._timed(plan, "fwd", plan._cur_stream, lambda: call("ym_conv_fwd", *conv, st))
         self._bn_fwd(plan, st, ss, sq)
 
+    def _bn_bwd_stats(self, plan, st, dy, fold=False):
+        """The BatchNorm backward's statistics pass over dy and z and its finalize (dgamma, dbeta, the apply
+        coefficients); fold: both in one launch (small maps: the last workgroup of each 64-channel group folds)."""
+        bn = self.m.bn
+        sc, sh, mu, rs = (self.bnv[i].data_ptr() for i in range(4))
+        if fold:
+            call("ym_bn_bwd_reduce_fold", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW,
+                 sc, sh, mu, rs, self.act, self.ps[0].data_ptr(), self.ps[1].data_ptr(), _p(bn.weight),
+                 plan.gptr(bn.weight), plan.gptr(bn.bias), 0, self.coef.data_ptr(), plan.bn_ws.data_ptr(), st)
+            return
+        call("ym_bn_bwd_reduce", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW, sc,
+             sh, mu, rs, self.act, self.ps[0].data_ptr(), self.ps[1].data_ptr(), st)
+        call("ym_bn_bwd_finalize", self.ps[0].data_ptr(), self.ps[1].data_ptr(), self.Gb, self.co, float(self.M),
+             _p(bn.weight), rs, plan.gptr(bn.weight), plan.gptr(bn.bias), 0, self.coef.data_ptr(),
+             plan.bn_ws.data_ptr(), st)
+
     def _bn_bwd(self, plan, st, dy):
         """BatchNorm (+ SiLU) backward: statistics pass over dy and z, finalize (dgamma, dbeta, apply
         coefficients), then dz = f(dy, z) written over z (+ the shortcut's gradient from the same dy
         read).  'bn' family: algorithmic bytes = dy + z read twice, dz written, partial rows, the
         shortcut gradient written (and read when it accumulates)."""
-        bn = self.m.bn
         sc, sh, mu, rs = (self.bnv[i].data_ptr() for i in range(4))
-        Gb = lib().ym_bn_bwd_blocks(self.M, self.co)
         r = self.res
         racc = r.grad_for_write(st) if r is not None else 0
         e = self.M * self.co * 2
-        work = 5 * e + 16 * Gb * self.co + ((2 + racc) * e if r is not None else 0)
+        work = 5 * e + 16 * self.Gb * self.co + ((2 + racc) * e if r is not None else 0)
 
-        fold = self.__dict__.get("_bwd_fold")
-        if fold is None:
-            fold = self._bwd_fold = bool(lib().ym_bn_bwd_fold_ok(self.M, self.co))
-        fold = fold and os.environ.get("YM_BWD_FOLD", "1") == "1"
+        if self._bwd_fold is None:
+            self._bwd_fold = bool(lib().ym_bn_bwd_fold_ok(self.M, self.co))
+        fold = self._bwd_fold and os.environ.get("YM_BWD_FOLD", "1") == "1"
 
         def run():
-            if fold:
-                # small maps: statistics + finalize in one launch (the last workgroup of each 64-channel group folds)
-                call("ym_bn_bwd_reduce_fold", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW,
-                     sc, sh, mu, rs, self.act, self.ps[0].data_ptr(), self.ps[1].data_ptr(), _p(bn.weight),
-                     plan.gptr(bn.weight), plan.gptr(bn.bias), 0, self.coef.data_ptr(), plan.bn_ws.data_ptr(), st)
-            else:
-                call("ym_bn_bwd_reduce", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW, sc,
-                     sh, mu, rs, self.act, self.ps[0].data_ptr(), self.ps[1].data_ptr(), st)
-                call("ym_bn_bwd_finalize", self.ps[0].data_ptr(), self.ps[1].data_ptr(), Gb, self.co, float(self.M),
-                     _p(bn.weight), rs, plan.gptr(bn.weight), plan.gptr(bn.bias), 0, self.coef.data_ptr(),
-                     plan.bn_ws.data_ptr(), st)
+            self._bn_bwd_stats(plan, st, dy, fold)
             if r is not None:
                 call("ym_bn_bwd_apply_res", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW, sc,
                      sh, mu, rs, self.act, self.coef.data_ptr(), self.z.data_ptr(), r.gptr(), r.bs, r.ld, racc, st)
@@ -438,25 +465,17 @@ class StemConvBN(ConvBN):
         oh, ow = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
         assert (oh, ow) == (y.H, y.W)
         self.M, self.HW, self.oh, self.ow = B * oh * ow, oh * ow, oh, ow
-        self.z = torch.empty(self.M, co, dtype=BF16, device=plan.dev)
-        self.G = 2048           # statistics rows = workgroups (2048 vs 1024: -22 us alone, +0.06-0.1 % step)
-        self.ps = torch.empty(2, max(self.G, lib().ym_bn_bwd_blocks(self.M, co)), co, dtype=F32, device=plan.dev)
-        self.bnv = torch.empty(4, co, dtype=F32, device=plan.dev)
-        self.coef = torch.empty(3, co, dtype=F32, device=plan.dev)
+        self._alloc(plan, 2048)   # statistics rows = workgroups (2048 vs 1024: -22 us alone, +0.06-0.1 % step)
 
     def _geo(self, plan):
         return (plan.B, self.H, self.W, self.oh, self.ow, self.co, self.s, 1)
 
     def forward(self, plan, st):
         y = self.y
-        if (not plan.training and os.environ.get("YM_EVAL_FUSE", "1") != "0" and y.ptr() % 16 == 0 and y.ld % 8 == 0
-                and y.bs % 8 == 0):
+        if not plan.training and os.environ.get("YM_EVAL_FUSE", "1") != "0" and self._eval_aligned():
             # eval: conv + running-statistics BatchNorm + SiLU in one launch (ym_conv_first_fwd_eval)
-            bn = self.m.bn
             (sc, sh, _, _), _, _, _ = self._static_args(plan)
-            if not plan.eval_coeff_batched:
-                call("ym_bn_eval_coeff", self.co, _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
-                     _p(bn.running_var), float(bn.eps), sc, sh, st)
+            self._eval_coeff(plan, st)
             call("ym_conv_first_fwd_eval", plan.img.data_ptr(), _p(self.m.conv.weight), sc, sh, self.act, y.ptr(),
                  y.bs, y.ld, plan.B, self.H, self.W, self.oh, self.ow, self.co, self.s, 1, self.ci, st)
             return
@@ -473,28 +492,21 @@ class StemConvBN(ConvBN):
         dy = self.y.grad_for_read(st)
         if self.co not in (16, 32, 64) or self.ci != 1:
             self._bn_bwd(plan, st, dy)
-            ws = plan.private_ws(self, lib().ym_conv_first_wgrad_workspace_size(self.co, self.ci))
+            ws = self._ws = plan.private_ws(self._ws, lib().ym_conv_first_wgrad_workspace_size(self.co, self.ci))
             call("ym_conv_first_wgrad", self.z.data_ptr(), plan.img.data_ptr(), plan.gptr(self.m.conv.weight),
                  plan.B, self.H, self.W, self.oh, self.ow, self.co, self.s, 1, self.ci, ws.data_ptr(),
                  ws.numel() * 4, st)
             plan.note_grad_write(plan._cur_stream)      # conv.weight: after the BN event _bn_bwd noted
             return
-        bn = self.m.bn
-        sc, sh, mu, rs = (self.bnv[i].data_ptr() for i in range(4))
-        Gb = lib().ym_bn_bwd_blocks(self.M, self.co)
-        ws = plan.private_ws(self, lib().ym_stem_bwd_wgrad_workspace_size(self.co))
+        ws = self._ws = plan.private_ws(self._ws, lib().ym_stem_bwd_wgrad_workspace_size(self.co))
         e = self.M * self.co * 2
 
         def run():
-            call("ym_bn_bwd_reduce", dy, self.y.bs, self.y.ld, self.z.data_ptr(), self.M, self.co, self.HW, sc, sh,
-                 mu, rs, self.act, self.ps[0].data_ptr(), self.ps[1].data_ptr(), st)
-            call("ym_bn_bwd_finalize", self.ps[0].data_ptr(), self.ps[1].data_ptr(), Gb, self.co, float(self.M),
-                 _p(bn.weight), rs, plan.gptr(bn.weight), plan.gptr(bn.bias), 0, self.coef.data_ptr(),
-                 plan.bn_ws.data_ptr(), st)
+            self._bn_bwd_stats(plan, st, dy)
             call("ym_stem_bwd_wgrad_stored", dy, self.y.bs, self.y.ld, self.z.data_ptr(), plan.img.data_ptr(),
                  self.bnv.data_ptr(), self.coef.data_ptr(), plan.gptr(self.m.conv.weight), ws.data_ptr(),
                  ws.numel() * 4, *self._geo(plan), st)
-        self._timed(plan, "bn", plan._cur_stream, run, 4 * e + 16 * Gb * self.co + 4 * plan.B * self.H * self.W)
+        self._timed(plan, "bn", plan._cur_stream, run, 4 * e + 16 * self.Gb * self.co + 4 * plan.B * self.H * self.W)
         plan.note_grad_write(plan._cur_stream)          # dgamma / dbeta and conv.weight are in the stream now
 
 
@@ -512,23 +524,15 @@ class DWConvBN(ConvBN):
         self.C, self.map = C, (hd, 2 * kd + hd, 2 * kd)     # gsz, gstride, goff
         self.k, self.co = 3, C
         self.M, self.HW = y.M, y.H * y.W
-        self.z = torch.empty(self.M, C, dtype=BF16, device=plan.dev)
-        self.G = 256
-        self.ps = torch.empty(2, max(self.G, lib().ym_bn_bwd_blocks(self.M, C)), C, dtype=F32, device=plan.dev)
-        self.bnv = torch.empty(4, C, dtype=F32, device=plan.dev)
-        self.coef = torch.empty(3, C, dtype=F32, device=plan.dev)
+        self._alloc(plan, 256)
 
     def forward(self, plan, st):
         gsz, gstr, goff = self.map
         y, r = self.y, self.res
-        if (not plan.training and os.environ.get("YM_EVAL_FUSE", "1") != "0" and y.ptr() % 16 == 0 and y.ld % 8 == 0
-                and y.bs % 8 == 0 and (r is None or (r.ptr() % 8 == 0 and r.ld % 4 == 0 and r.bs % 4 == 0))):
+        if not plan.training and os.environ.get("YM_EVAL_FUSE", "1") != "0" and self._eval_aligned():
             # eval: depthwise conv + running-statistics BatchNorm + the residual in one launch (ym_dw3x3_fwd_eval)
-            bn = self.m.bn
             (sc, sh, _, _), _, _, _ = self._static_args(plan)
-            if not plan.eval_coeff_batched:
-                call("ym_bn_eval_coeff", self.co, _p(bn.weight), _p(bn.bias), _p(bn.running_mean),
-                     _p(bn.running_var), float(bn.eps), sc, sh, st)
+            self._eval_coeff(plan, st)
             call("ym_dw3x3_fwd_eval", self.x.ptr(), self.x.bs, self.x.ld, gsz, gstr, goff, _p(self.m.conv.weight), sc,
                  sh, self.act, r.ptr() if r is not None else None, r.bs if r is not None else 0,
                  r.ld if r is not None else 0, y.ptr(), y.bs, y.ld, plan.B, y.H, y.W, self.C, st)
@@ -549,7 +553,7 @@ class DWConvBN(ConvBN):
             vch[self.x.c0 + h * hs + goff: self.x.c0 + h * hs + goff + hd] = True
         acc = int(self.x.act.written[vch].all())
         gsz, gstr, goff = self.map
-        ws = plan.private_ws(self, lib().ym_dw3x3_bwd_workspace_size(self.C))
+        ws = self._ws = plan.private_ws(self._ws, lib().ym_dw3x3_bwd_workspace_size(self.C))
         call("ym_dw3x3_bwd", self.x.ptr(), self.x.bs, self.x.ld, gsz, gstr, goff, _p(self.m.conv.weight),
              self.z.data_ptr(), self.x.gptr(), self.x.bs, self.x.ld, plan.gptr(self.m.conv.weight), plan.B, self.y.H,
              self.y.W, self.C, acc, ws.data_ptr(), ws.numel() * 4, st)
@@ -607,14 +611,13 @@ class SPPFPools:
             return [_ka(sl[0])], [_ka(v) for v in sl[1:]]
         return [_kg(v) for v in sl[1:]], [_kg(v) for v in sl]
 
-    def __init__(self, plan, cv1_op, slices):
-        self.slices = slices                      # [s0 (cv1 out), s1, s2, s3]
+    def __init__(self, plan, slices):
+        self.slices = slices                      # [s0 (cv1 out, which cv1 also writes to P[0]), s1, s2, s3]
         x = slices[0]
         self.M, self.C, self.H, self.W = x.M, x.c, x.H, x.W
         self.P = torch.empty(4, self.M, self.C, dtype=F32, device=plan.dev)   # fp32 chain values
         self.code = torch.empty(3, self.M, self.C, dtype=torch.uint8, device=plan.dev)   # window argmax
         self.G = torch.empty(2, self.M, self.C, dtype=F32, device=plan.dev)   # grad ping-pong
-        cv1_op.out32 = self.P[0]
 
     def fused(self, plan):
         """The whole chain in one launch per direction (ym_sppf_fwd / _bwd, chain kept in LDS) when
@@ -727,6 +730,7 @@ class HeadLevel:
         self.dzb = torch.empty(self.M, 64, dtype=BF16, device=plan.dev)
         self.dzc = torch.empty(self.M, ncp, dtype=BF16, device=plan.dev)
         self.wsc = torch.empty(ncp, xc.c, dtype=F32, device=plan.dev)
+        self._ws = None           # ym_head_grad's partial rows
 
         def desc(x, cout, y_bs, y_ld, out_f32):
             d = ConvDesc()
@@ -750,7 +754,7 @@ class HeadLevel:
 
     def backward(self, plan, st):
         B, A, no = self.head.shape
-        ws = plan.private_ws(self, lib().ym_head_grad_workspace_size())
+        ws = self._ws = plan.private_ws(self._ws, lib().ym_head_grad_workspace_size())
         call("ym_head_grad", plan.dhead.data_ptr(), A, self.a_off, self.HW, self.M, self.nc, self.dzb.data_ptr(),
              self.dzc.data_ptr(), plan.gptr(self.box.bias), plan.gptr(self.cls.bias), ws.data_ptr(), ws.numel() * 4,
              st)
@@ -782,27 +786,93 @@ def op_params(op):
     return [p for m in mods for p in m.parameters() if p.requires_grad]
 
 
+# ----------------------------------------------------------------------------- stream scheduler
+def schedule(rws, K):
+    """Streams for a list of ops given as their (reads, writes) buffer ranges, in issue order, over K streams:
+    ([(stream, [ops whose events it waits for])] per op, {ops that record an event}).  An op depends on the earlier ops
+    that wrote a range it reads or writes and on those that read a range it writes; it waits only for the latest of them
+    on each other stream.  The stream policy is described at Plan._nstreams."""
+    writes, reads, deps = [], [], []
+    for i, (R, W) in enumerate(rws):
+        d = set()
+        for k in R:
+            d.update(j for k2, j in writes if _overlap(k, k2))
+        for k in W:
+            d.update(j for k2, j in writes if _overlap(k, k2))
+            d.update(j for k2, j in reads if _overlap(k, k2))
+        deps.append(d)
+        writes.extend((k, i) for k in W)
+        reads.extend((k, i) for k in R)
+    stream_of, tail, plan = [0] * len(rws), [-1] * K, []
+    need_ev = set()
+    for i, d in enumerate(deps):
+        s = 0
+        if d:
+            j = max(d)
+            s = stream_of[j]
+            if tail[s] != j:
+                cands = [t for t in range(K) if tail[t] in d]
+                s = max(cands, key=lambda t: tail[t]) if cands else min(range(K), key=lambda t: tail[t])
+        elif i > 0:
+            s = min(range(K), key=lambda t: tail[t])
+        waits = {}
+        for j in d:
+            if stream_of[j] != s:
+                waits[stream_of[j]] = max(waits.get(stream_of[j], -1), j)
+        stream_of[i] = s
+        tail[s] = i
+        need_ev.update(waits.values())
+        plan.append((s, sorted(waits.values())))
+    return plan, need_ev
+
+
 # ----------------------------------------------------------------------------- plan
 class Plan:
-    def __init__(self, root, B, H, W, dev, training):
-        self.root, self.B, self.dev, self.training = root, B, dev, training
+    """One lowered module tree at one input shape.  kind: "model" (the whole YOLOv11, lower_model: the only kind whose
+    phases are replayed as HIP graphs), "block" (one building block, block_plan) or "detect" (Detect on its own level
+    maps, detect_plan).  Every attribute of a plan is assigned here; the lowering fills the first group."""
+
+    def __init__(self, root, B, H, W, dev, training, kind):
+        assert kind in ("model", "block", "detect"), kind
+        self.root, self.B, self.dev, self.training, self.kind = root, B, dev, training, kind
         self.eval_coeff_batched = not training and dev.type == "cuda"   # one launch for every layer
         self.acts, self.ops = [], []
         self.weights = WeightStore(self)
+        # --- what the lowering sets
+        self.inputs = []           # NHWC input Views the caller's tensors are copied into (none: the stem reads img)
+        self.frozen = []           # input Acts whose gradient nobody needs (needs_grad)
+        self.output = None         # block plans: the output View, whose gradient the caller writes (the backward's seed)
+        self.img = None            # fp32 NCHW image of a plan that starts at the stem
+        self.head = None           # (B, A, 64+nc) fp32 head buffer (model and detect plans)
+        self.dhead = None          # its gradient, set by the caller before backward()
+        self.level_hw = None       # [(H, W)] of the head's levels
+        self.layer_outs = None     # model plans: the output View of every yaml layer
+        # --- hooks of the bench, the tools and data parallelism
         self.probe, self.probe_events = None, []   # bench: time one op's conv launch
         self.family_events = None  # bench: {'fwd'|'dgrad'|'wgrad': [(ev0, ev1, op)]} for every ConvBN launch
-        self._bn_ws = []           # one BN-reduction workspace per scheduler stream (see bn_ws)
-        self._cur = 0              # scheduler stream the current op runs on
-        self.input = None          # View for block plans
-        self.img = None            # fp32 image for the full model
-        self.head = None           # (B, A, 64+nc) fp32 for the full model
-        self.dhead = None
-        self._scratch = []
-        self.grad_hook = None      # called with each op's finished parameters during backward (DP buckets)
-        self._writes = []          # (stream, event) after each parameter-gradient write of the current op
         self.on_op = None          # tools: called with (op index, op, phase) before each op runs (launch maps)
-        self.side_stream = None    # weight-gradient stream (see side())
+        self.grad_hook = None      # called with each op's finished parameters during backward (DP buckets)
+        # --- run state
+        self.gen = 0               # forwards run so far (check_generation)
+        self._pending = None       # weak reference to the autograd node of a forward whose backward has not run
+        self._cur = 0              # scheduler stream the current op runs on
         self._cur_stream = None    # torch stream the current op is issued on (scheduler)
+        self._op_pos = 0           # position of the current op in the list being run
+        self._writes = []          # (stream, event) after each parameter-gradient write of the current op
+        self._wevents = {}         # (op position, write) -> the persistent event of note_grad_write
+        self.side_stream = None    # weight-gradient stream (see side())
+        self._link_events = {}     # source stream -> the persistent event of _link
+        self._sched = {}           # (phase, K, number of ops) -> schedule()
+        self._dag_streams = []     # the scheduler's streams beyond the caller's
+        self._active_streams = []  # streams of the last _run (comm_streams)
+        self._events = {}          # phase -> {op position: the event later ops on other streams wait for}
+        self._bn_ws = []           # one BN-reduction workspace per scheduler stream (see bn_ws)
+        self._wg_bytes = 0         # split-K workspace the largest ym_conv_wgrad of the plan needs
+        self._wg_ws = {}           # scheduler stream (-1: the side stream) -> that workspace
+        self._graphs = {}          # phase -> (captured graph, its static input tensors, _graph_key at capture)
+        self._eager_keys = {}      # phase -> _graph_key of the last eager run
+        self._gk_pairs = None      # (module dictionary, name) of every parameter and buffer (_graph_key)
+        self._eval_key, self._eval_table, self._eval_n = None, None, 0     # pointer table of _eval_coeffs
         # flat parameter-gradient buffer; each .grad is a view of it
         params = [p for p in root.parameters() if p.requires_grad]
         self.params = params
@@ -832,10 +902,9 @@ class Plan:
         (re-recorded each time).  torch's wait_stream records a temporary event that is destroyed right
         after the wait; inside a HIP graph capture the runtime still refers to it at hipStreamEndCapture,
         which then crashed once the capture held several such joins (the 3-stream forward capture)."""
-        evs = self.__dict__.setdefault("_link_events", {})
-        ev = evs.get(src.cuda_stream)
+        ev = self._link_events.get(src.cuda_stream)
         if ev is None:
-            ev = evs[src.cuda_stream] = torch.cuda.Event()
+            ev = self._link_events[src.cuda_stream] = torch.cuda.Event()
         ev.record(src)
         dst.wait_event(ev)
 
@@ -846,11 +915,10 @@ class Plan:
         persistent event per (op position, write), re-recorded every step."""
         if self.grad_hook is None or stream is None:
             return
-        evs = self.__dict__.setdefault("_wevents", {})
         key = (self._op_pos, len(self._writes))
-        ev = evs.get(key)
+        ev = self._wevents.get(key)
         if ev is None:
-            ev = evs[key] = torch.cuda.Event()
+            ev = self._wevents[key] = torch.cuda.Event()
         ev.record(stream)
         self._writes.append((stream, ev))
 
@@ -879,16 +947,16 @@ class Plan:
     def act(self, C, H, W, name=""):
         return View(Act(self, C, H, W, name=name))
 
-    def private_ws(self, op, nbytes):
-        """An op's own fp32 scratch (partial rows of its fixed-order reductions), allocated once."""
-        ws = op.__dict__.get("_ws")
+    def private_ws(self, ws, nbytes):
+        """An op's own fp32 scratch (partial rows of its fixed-order reductions), which the op keeps: `ws` itself once
+        it holds nbytes."""
         if ws is None or ws.numel() * 4 < nbytes:
-            ws = op.__dict__["_ws"] = torch.empty(max((nbytes + 3) // 4, 1), dtype=F32, device=self.dev)
+            ws = torch.empty(max((nbytes + 3) // 4, 1), dtype=F32, device=self.dev)
         return ws
 
     def need_wgrad_ws(self, desc):
         """Size the shared split-K workspace of ym_conv_wgrad (ops run in order on one stream)."""
-        self._wg_bytes = max(getattr(self, "_wg_bytes", 0), int(lib().ym_conv_wgrad_workspace_size(ctypes.byref(desc))))
+        self._wg_bytes = max(self._wg_bytes, int(lib().ym_conv_wgrad_workspace_size(ctypes.byref(desc))))
 
     def _alloc_bn_ws(self, K):
         """Allocate the BN scratch of K scheduler streams, zeroed once (the one-launch finalize's
@@ -910,10 +978,9 @@ class Plan:
         """Split-K scratch of ym_conv_wgrad: one for the side stream (wgrads run there in order), or
         one per scheduler stream when they run in line."""
         key = -1 if self.side_stream is not None else self._cur
-        wss = self.__dict__.setdefault("_wg_ws", {})
-        if key not in wss:
-            wss[key] = torch.empty(max(self._wg_bytes // 4, 1), dtype=F32, device=self.dev)
-        return wss[key]
+        if key not in self._wg_ws:
+            self._wg_ws[key] = torch.empty(max(self._wg_bytes // 4, 1), dtype=F32, device=self.dev)
+        return self._wg_ws[key]
 
     def grad_view(self, p):
         return self.grad_views[id(p)]
@@ -924,7 +991,8 @@ class Plan:
         return self.grad_views[id(p)].data_ptr()
 
     def needs_grad(self, v: View):
-        return v.act is not None and (v.act is not getattr(self.input, "act", None) or self.input_requires_grad)
+        """Whether the backward forms the gradient of v: everything but the inputs the lowering froze."""
+        return v.act not in self.frozen
 
     # --------------------------------------------------------------- stream scheduler
     # The op list is a DAG over buffer ranges (each op declares what it reads and writes, `rw`):
@@ -943,58 +1011,23 @@ class Plan:
             # streams captured, same box, profiles/r05/eval_graph_streams.txt: the replayed cross-stream edges cost
             # more than the overlap they allow at these sizes)
             return 1
-        k = max(1, int(os.environ.get("YM_STREAMS", "3")))
-        return k
+        return max(1, int(os.environ.get("YM_STREAMS", "3")))
 
     def _schedule(self, ops, phase, K):
         key = (phase, K, len(ops))
-        cache = self.__dict__.setdefault("_sched", {})
-        if key in cache:
-            return cache[key]
-        rws = [op.rw(self, phase) for op in ops]
-        writes, reads, deps = [], [], []
-        for i, (R, W) in enumerate(rws):
-            d = set()
-            for k in R:
-                d.update(j for k2, j in writes if _overlap(k, k2))
-            for k in W:
-                d.update(j for k2, j in writes if _overlap(k, k2))
-                d.update(j for k2, j in reads if _overlap(k, k2))
-            deps.append(d)
-            writes.extend((k, i) for k in W)
-            reads.extend((k, i) for k in R)
-        stream_of, tail, plan = [0] * len(ops), [-1] * K, []
-        need_ev = set()
-        for i, d in enumerate(deps):
-            s = 0
-            if d:
-                j = max(d)
-                s = stream_of[j]
-                if tail[s] != j:
-                    cands = [t for t in range(K) if tail[t] in d]
-                    s = max(cands, key=lambda t: tail[t]) if cands else min(range(K), key=lambda t: tail[t])
-            elif i > 0:
-                s = min(range(K), key=lambda t: tail[t])
-            waits = {}
-            for j in d:
-                if stream_of[j] != s:
-                    waits[stream_of[j]] = max(waits.get(stream_of[j], -1), j)
-            stream_of[i] = s
-            tail[s] = i
-            need_ev.update(waits.values())
-            plan.append((s, sorted(waits.values())))
-        cache[key] = (plan, need_ev)
-        return cache[key]
+        if key not in self._sched:
+            self._sched[key] = schedule([op.rw(self, phase) for op in ops], K)
+        return self._sched[key]
 
     def _streams(self, K):
-        ss = self.__dict__.setdefault("_dag_streams", [])
+        ss = self._dag_streams
         while len(ss) < K - 1:
             ss.append(torch.cuda.Stream(device=self.dev))
         return [torch.cuda.current_stream(self.dev)] + ss[:K - 1]
 
     def comm_streams(self):
         """Every stream a backward writes gradients from (the DP buckets join them before a collective)."""
-        out = list(self.__dict__.get("_active_streams", []))
+        out = list(self._active_streams)
         if self.side_stream is not None:
             out.append(self.side_stream)
         return out
@@ -1004,6 +1037,7 @@ class Plan:
         if phase == "fwd" and os.environ.get("YM_FWD_STREAMS"):
             K = max(1, int(os.environ["YM_FWD_STREAMS"]))      # A/B runs: the forward's stream count alone
         self._alloc_bn_ws(K)
+        fwd = phase == "fwd"
         if K == 1:
             st = stream_ptr(self.dev)
             self._cur = 0
@@ -1013,19 +1047,18 @@ class Plan:
                 self._op_pos = i
                 if self.on_op is not None:
                     self.on_op(i, op, phase)
-                getattr(op, phase == "fwd" and "forward" or "backward")(self, st)
+                (op.forward if fwd else op.backward)(self, st)
                 if after is not None:
                     after(op)
             return
         sched, need_ev = self._schedule(ops, phase, K)
         streams = self._streams(K)
         self._active_streams = streams
-        evs = self.__dict__.setdefault("_events", {}).setdefault(phase, {})
+        evs = self._events.setdefault(phase, {})
         main = streams[0]
         for s in streams[1:]:
             self._link(s, main)
         ptrs = [s.cuda_stream for s in streams]
-        fwd = phase == "fwd"
         # HIP graph capture (ROCm 7.2 runtime) segfaults in hipStreamEndCapture once two non-origin streams
         # have waited on each other's events (tools/hip_graph_repro.py `cycle`: s2 waits on s1, later s1 on
         # s2 — four torch calls, no yolomi code).  While capturing, such a wait is relayed through the origin
@@ -1047,10 +1080,7 @@ class Plan:
             self._op_pos = i
             if self.on_op is not None:
                 self.on_op(i, op, phase)
-            if fwd:
-                op.forward(self, ptrs[k])
-            else:
-                op.backward(self, ptrs[k])
+            (op.forward if fwd else op.backward)(self, ptrs[k])
             if after is not None:
                 after(op)
             if i in need_ev:
@@ -1079,7 +1109,7 @@ class Plan:
     # call compares the pointers of the model's parameters and buffers with the captured ones
     # (_graph_key) and re-captures after an eager run when one was replaced.
     def _graph_ok(self):
-        if not (self.dev.type == "cuda" and getattr(self, "is_model", False) and self.probe is None
+        if not (self.dev.type == "cuda" and self.kind == "model" and self.probe is None
                 and self.family_events is None):
             return False
         if self.training:
@@ -1089,7 +1119,7 @@ class Plan:
     def _graph_key(self):
         """Data pointers of every parameter and buffer of the model, looked up in the modules' live
         dictionaries (a replaced Parameter / buffer is seen)."""
-        pairs = self.__dict__.get("_gk_pairs")
+        pairs = self._gk_pairs
         if pairs is None:
             pairs = self._gk_pairs = []
             for mod in self.root.modules():
@@ -1110,8 +1140,7 @@ class Plan:
         A capture only follows an eager run over the same parameter / buffer pointers: the eager run
         rebuilds the pointer tables (weight preparation, eval coefficients) and uploads them, which a
         capture must not do.  A replaced parameter or buffer drops the graph (eager, then capture again)."""
-        graphs = self.__dict__.setdefault("_graphs", {})
-        eager_keys = self.__dict__.setdefault("_eager_keys", {})
+        graphs, eager_keys = self._graphs, self._eager_keys
         if not self._graph_ok():
             body()
             return
@@ -1151,12 +1180,12 @@ class Plan:
         """Eval: every BatchNorm layer's scale / shift from its running statistics in ONE launch
         (ym_bn_eval_coeff_batch over a pointer table built once per plan; the parameters and buffers
         are read at launch time, so later weight / statistics updates are picked up)."""
-        ents = [op for op in self.ops if hasattr(op, "bnv") and hasattr(op, "m")]
+        ents = [op for op in self.ops if isinstance(op, ConvBN)]
         # keyed on EVERY pointer the table holds: a parameter or buffer replaced by a new tensor
         # (load_state_dict(assign=True), bn.running_var = ...) rebuilds it instead of leaving a dangling one
         key = tuple((_p(op.m.bn.weight), _p(op.m.bn.bias), _p(op.m.bn.running_mean), _p(op.m.bn.running_var),
                      op.bnv.data_ptr()) for op in ents)
-        if getattr(self, "_eval_key", None) != key:
+        if self._eval_key != key:
             arr = (BnEvalEntry * len(ents))()
             for e, op in zip(arr, ents):
                 bn = op.m.bn
@@ -1178,7 +1207,19 @@ class Plan:
             self._run(self.ops, "fwd")
         self._replay("fwd", body, [("img", self.img)] if self.img is not None else [])
 
+    def forward_on(self, xs):
+        """One forward on the caller's fp32 NCHW tensors (the image of a plan that starts at the stem, else one per
+        input view, copied into its NHWC buffer); returns the forward's generation."""
+        if not self.inputs:
+            self.img = xs[0].float().contiguous()
+        for v, x in zip(self.inputs, xs):
+            v.act.t.copy_(x.permute(0, 2, 3, 1))
+        self.forward()
+        return self.new_generation()
+
     def backward(self):
+        """The backward of every kind of plan.  dhead (model, detect) or the gradient of `output` (block) is the
+        caller's to write first; parameter gradients land in grad_flat, input gradients in the inputs' Acts."""
         # gradient accumulation without zero_grad(): the parameters' .grad still alias this plan's flat
         # buffer (install_grads) and hold the previous backward's sum, which the zero fill of the backward
         # would drop — keep it and add it back after this backward (single-process; under DP the buffer is
@@ -1186,8 +1227,7 @@ class Plan:
         # Decided and done eagerly, OUTSIDE the body a HIP graph captures and replays (YM_GRAPH=1): a
         # captured decision would replay a stale keep buffer, or none, on every later step.
         keep = self._accumulation_keep()
-        self._replay("bwd", lambda: self._backward_ops(self.ops),
-                     [("dhead", self.dhead)] if self.dhead is not None else [])
+        self._replay("bwd", self._backward_ops, [("dhead", self.dhead)] if self.dhead is not None else [])
         if keep is not None:
             self.grad_flat.add_(keep)
 
@@ -1198,16 +1238,16 @@ class Plan:
                 return self.grad_flat.clone()
         return None
 
-    def _backward_ops(self, ops):
+    def _backward_ops(self):
         for a in self.acts:
             a.written[:] = False
         self.grad_flat.zero_()
-        for t in self._scratch:
-            t.zero_()
+        if self.output is not None:
+            self.output.mark()          # a block plan's seed: the caller wrote the output's gradient
         hook = None if self._graph_ok() else self.grad_hook
         self._begin_side()
         self._writes = []
-        self._run(list(reversed(ops)), "bwd",
+        self._run(list(reversed(self.ops)), "bwd",
                   (lambda op: hook(op_params(op), self.take_grad_writes(op))) if hook is not None else None)
         self._join_side()
 
@@ -1221,11 +1261,11 @@ class Plan:
     # run another forward raises instead of returning wrong gradients, and so does a second backward
     # through one forward (the backward overwrites z with dz in place).
     def new_generation(self):
-        self.gen = getattr(self, "gen", 0) + 1
+        self.gen += 1
         return self.gen
 
     def check_generation(self, gen):
-        if gen != getattr(self, "gen", 0):
+        if gen != self.gen:
             raise YolomiError("backward of a forward whose activations a newer forward of the same input shape has "
                               "overwritten: run backward (or detach the outputs) before the next forward")
 
@@ -1234,8 +1274,7 @@ class Plan:
 
     @property
     def pending(self):
-        r = self.__dict__.get("_pending")
-        return r is not None and r() is not None
+        return self._pending is not None and self._pending() is not None
 
     def install_grads(self):
         """Expose the flat buffer as parameter .grad (accumulating if a grad already exists)."""
@@ -1248,14 +1287,14 @@ class Plan:
 
 
 # ----------------------------------------------------------------------------- lowering
-def _conv(plan, m, x: View, out: View | None = None, res=None, act=None):
+def _conv(plan, m, x: View, out: View | None = None, res=None, act=None, out32=None):
     k, s = m.conv.kernel_size[0], m.conv.stride[0]
     co = m.conv.out_channels
     H, W = (x.H + 2 * (k // 2) - k) // s + 1, (x.W + 2 * (k // 2) - k) // s + 1
     y = out if out is not None else plan.act(co, H, W)
     if act is None:
         act = not isinstance(m.act, torch.nn.Identity)
-    plan.ops.append(ConvBN(plan, m, x, y, s, act, res))
+    plan.ops.append(ConvBN(plan, m, x, y, s, act, res, out32))
     return y
 
 
@@ -1292,8 +1331,9 @@ def _c2f(plan, m, x: View, out=None):
 def _sppf(plan, m, x: View, out=None):
     c_ = m.cv1.conv.out_channels
     cat = plan.act(4 * c_, x.H, x.W)
-    _conv(plan, m.cv1, x, cat.sub(0, c_))
-    plan.ops.append(SPPFPools(plan, plan.ops[-1], [cat.sub(j * c_, c_) for j in range(4)]))
+    pools = SPPFPools(plan, [cat.sub(j * c_, c_) for j in range(4)])
+    _conv(plan, m.cv1, x, cat.sub(0, c_), out32=pools.P[0])      # the pools read cv1's output in fp32
+    plan.ops.append(pools)
     return _conv(plan, m.cv2, cat, out)
 
 
@@ -1451,9 +1491,7 @@ class _ModelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, anchor, plan):
-        plan.img = img.contiguous()
-        plan.forward()
-        ctx.plan, ctx.gen = plan, plan.new_generation()
+        ctx.plan, ctx.gen, ctx.done = plan, plan.forward_on([img]), False
         plan.set_pending(ctx)
         return plan.head.detach()
 
@@ -1461,7 +1499,7 @@ class _ModelFn(torch.autograd.Function):
     def backward(ctx, dhead):
         plan = ctx.plan
         plan.check_generation(ctx.gen)
-        if getattr(ctx, "done", False):
+        if ctx.done:
             raise YolomiError("a second backward through one forward (retain_graph=True): the first backward "
                               "consumed the forward's activations in place; run the forward again")
         ctx.done = True
@@ -1477,12 +1515,7 @@ class _BlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, anchor, plan):
-        if plan.stem:
-            plan.img = x.float().contiguous()
-        else:
-            plan.input.act.t.copy_(x.permute(0, 2, 3, 1))
-        plan.forward()
-        ctx.plan, ctx.gen = plan, plan.new_generation()
+        ctx.plan, ctx.gen = plan, plan.forward_on([x])
         out = plan.output.act.t[..., plan.output.c0:plan.output.c0 + plan.output.c]
         return out.permute(0, 3, 1, 2).float().contiguous()
 
@@ -1493,10 +1526,27 @@ class _BlockFn(torch.autograd.Function):
         o = plan.output
         g = o.act.grad()
         g[..., o.c0:o.c0 + o.c].copy_(dy.permute(0, 2, 3, 1))
-        plan.backward_from_output()
+        plan.backward()
         plan.install_grads()
-        dx = plan.input.act.grad().permute(0, 3, 1, 2).float() if plan.input_requires_grad else None
-        return dx, None, None
+        dx = [v.act.grad().permute(0, 3, 1, 2).float() for v in plan.inputs if plan.needs_grad(v)]
+        return (dx[0] if dx else None), None, None
+
+
+def block_plan(module, shape, dev, input_requires_grad):
+    """The plan of one building block on a (B, C, H, W) input."""
+    B, C, H, W = shape
+    plan = Plan(module, B, H, W, dev, module.training, "block")
+    if type(module).__name__ == "Conv" and module.conv.in_channels <= 4 and module.conv.kernel_size[0] == 3:
+        # stem conv reads the fp32 image directly (no input view, no input gradient)
+        k, s = module.conv.kernel_size[0], module.conv.stride[0]
+        plan.output = plan.act(module.conv.out_channels, (H + 2 * (k // 2) - k) // s + 1,
+                               (W + 2 * (k // 2) - k) // s + 1)
+        plan.ops.append(StemConvBN(plan, module, (B, H, W), plan.output, s))
+    else:
+        plan.inputs = [plan.act(C, H, W, name="input")]
+        plan.frozen = [] if input_requires_grad else [plan.inputs[0].act]
+        plan.output = lower_block(plan, module, plan.inputs[0])
+    return plan
 
 
 def run_block(module, x: torch.Tensor):
@@ -1508,34 +1558,7 @@ def run_block(module, x: torch.Tensor):
     cache = module.__dict__.setdefault("_ym_plans", {})
     plan = cache.get(key)
     if plan is None:
-        plan = Plan(module, B, H, W, x.device, module.training)
-        if type(module).__name__ == "Conv" and module.conv.in_channels <= 4 and module.conv.kernel_size[0] == 3:
-            # stem conv reads the fp32 image directly (no input gradient)
-            plan.stem = True
-            plan.input = None
-            plan.input_requires_grad = False
-            k, s = module.conv.kernel_size[0], module.conv.stride[0]
-            plan.output = plan.act(module.conv.out_channels, (H + 2 * (k // 2) - k) // s + 1,
-                                   (W + 2 * (k // 2) - k) // s + 1)
-            plan.ops.append(StemConvBN(plan, module, (B, H, W), plan.output, s))
-        else:
-            plan.stem = False
-            plan.input = plan.act(C, H, W, name="input")
-            plan.input_requires_grad = x.requires_grad
-            plan.output = lower_block(plan, module, plan.input)
-
-        def backward_from_output():
-            for a in plan.acts:
-                a.written[:] = False
-            plan.grad_flat.zero_()
-            for t in plan._scratch:
-                t.zero_()
-            plan.output.mark()
-            plan._begin_side()
-            plan._run(list(reversed(plan.ops)), "bwd")
-            plan._join_side()
-        plan.backward_from_output = backward_from_output
-        cache[key] = plan
+        plan = cache[key] = block_plan(module, x.shape, x.device, x.requires_grad)
     anchor = module.__dict__.setdefault("_ym_anchor", torch.zeros(1, requires_grad=True))
     return _BlockFn.apply(x, anchor, plan)
 
@@ -1545,10 +1568,7 @@ class _DetectFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, plan, *xs):
-        for v, x in zip(plan.inputs, xs):
-            v.act.t.copy_(x.permute(0, 2, 3, 1))
-        plan.forward()
-        ctx.plan, ctx.gen = plan, plan.new_generation()
+        ctx.plan, ctx.gen = plan, plan.forward_on(xs)
         ctx.needs = [x.requires_grad for x in xs]
         return plan.head.clone()
 
@@ -1557,10 +1577,23 @@ class _DetectFn(torch.autograd.Function):
         plan = ctx.plan
         plan.check_generation(ctx.gen)
         plan.dhead = dhead.contiguous()
-        plan.backward_from_head()
+        plan.backward()
         plan.install_grads()
         dxs = [v.act.grad().permute(0, 3, 1, 2).float() if need else None for v, need in zip(plan.inputs, ctx.needs)]
         return (None, None, *dxs)
+
+
+def detect_plan(det, shapes, dev):
+    """The plan of Detect on level maps of the (B, C, H, W) `shapes`.  Every level input takes part in the backward
+    (nothing is frozen), whichever of the caller's maps require a gradient."""
+    B = shapes[0][0]
+    plan = Plan(det, B, shapes[0][2], shapes[0][3], dev, det.training, "detect")
+    plan.inputs = [plan.act(C, H, W, name=f"level{i}") for i, (_, C, H, W) in enumerate(shapes)]
+    plan.level_hw = [(H, W) for _, _, H, W in shapes]
+    plan.head = torch.empty(B, sum(H * W for H, W in plan.level_hw), det.no, dtype=F32, device=dev)
+    plan.dhead = torch.empty_like(plan.head)
+    _detect(plan, det, plan.inputs, plan.head)
+    return plan
 
 
 def run_detect(det, xs):
@@ -1571,39 +1604,17 @@ def run_detect(det, xs):
         raise YolomiError("yolomi kernels run on the MI355X only (got a CPU tensor)")
     if len(xs) != det.nl:
         raise YolomiError(f"Detect expects {det.nl} level maps, got {len(xs)}")
-    B = xs[0].shape[0]
     key = ("detect", tuple(tuple(x.shape) for x in xs), det.training, tuple(x.requires_grad for x in xs))
     cache = det.__dict__.setdefault("_ym_plans", {})
     plan = cache.get(key)
     if plan is None:
-        plan = Plan(det, B, xs[0].shape[2], xs[0].shape[3], xs[0].device, det.training)
-        plan.inputs = [plan.act(x.shape[1], x.shape[2], x.shape[3], name=f"level{i}") for i, x in enumerate(xs)]
-        plan.input = None
-        plan.input_requires_grad = any(x.requires_grad for x in xs)
-        A = sum(x.shape[2] * x.shape[3] for x in xs)
-        plan.head = torch.empty(B, A, det.no, dtype=F32, device=plan.dev)
-        plan.dhead = torch.empty_like(plan.head)
-        _detect(plan, det, plan.inputs, plan.head)
-        plan.level_hw = [(x.shape[2], x.shape[3]) for x in xs]
-
-        def backward_from_head():
-            keep = plan._accumulation_keep()
-            plan._backward_ops(plan.ops)
-            if keep is not None:
-                plan.grad_flat.add_(keep)
-        plan.backward_from_head = backward_from_head
-        cache[key] = plan
-    # every level input takes part in the backward (needs_grad checks plan.input only)
-    plan.needs_grad = lambda v: v.act is not None
+        plan = cache[key] = detect_plan(det, [tuple(x.shape) for x in xs], xs[0].device)
     anchor = det.__dict__.setdefault("_ym_anchor", torch.zeros(1, device=xs[0].device, requires_grad=True))
     xs32 = [x.float().contiguous() for x in xs]
     if torch.is_grad_enabled() and det.training:
         head = _DetectFn.apply(anchor, plan, *xs32)
     else:
-        for v, x in zip(plan.inputs, xs32):
-            v.act.t.copy_(x.permute(0, 2, 3, 1))
-        plan.forward()
-        plan.new_generation()
+        plan.forward_on(xs32)
         head = plan.head.clone()
     return head, plan
 
@@ -1623,10 +1634,7 @@ def run_model(model, img: torch.Tensor):
     # the first plan of this shape whose activations no pending backward still needs (see Plan.pending)
     plan = next((p for p in pool if not p.pending), None)
     if plan is None:
-        plan = Plan(model, B, H, W, img.device, model.training)
-        plan.input_requires_grad = False
-        plan.is_model = True
-        lower_model(plan, model, (B, H, W))
+        plan = lower_model(Plan(model, B, H, W, img.device, model.training, "model"), model, (B, H, W))
         pool.append(plan)
     if model.training and torch.is_grad_enabled() and any(p_.pending for p_ in pool if p_ is not plan):
         # several forwards in flight THIS step: their gradients meet in .grad (install_grads adds), so data
@@ -1640,9 +1648,7 @@ def run_model(model, img: torch.Tensor):
     if torch.is_grad_enabled() and model.training:
         head = _ModelFn.apply(img32, anchor, plan)
     else:
-        plan.img = img32.contiguous()
-        plan.forward()
-        plan.new_generation()
+        plan.forward_on([img32])
         # a fresh tensor: the plan's buffer is rewritten by the next forward of this shape
         head = plan.head.clone()
     return head, plan
