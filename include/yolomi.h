@@ -610,9 +610,19 @@ typedef struct ym_tile_entry {
     int32_t src;               /* image index into meta; outside [0, n_images): an all-fill tile, no candidates */
     int32_t x0, y0, tw, th;    /* the window in source pixels */
     int32_t nw, nh, left, top; /* the window resized to nw x nh, first pixel at (left, top) of the frame */
-    int32_t edges;             /* bit 0 left, 1 right, 2 top, 3 bottom: that window side is interior */
+    int32_t edges;             /* bit 0 left, 1 right, 2 top, 3 bottom: that window side is interior; bits 4 and 5:
+                                * YM_TILE_MIRROR_X / _Y below; bits 6 and above are ignored */
     float sx, sy;              /* frame pixels -> window pixels */
 } ym_tile_entry;               /* 48 bytes */
+/* Mirrored views (test-time augmentation), in `edges`.  Render: frame pixel (x, y) inside [left, left + nw)
+ * x [top, top + nh) shows what the entry without the bit shows at column left + nw - 1 - (x - left) (MIRROR_X) / row
+ * top + nh - 1 - (y - top) (MIRROR_Y): the tile is, bit for bit, the unmirrored tile with the columns (rows) of that
+ * rectangle reversed, in the copy case and in the resized case.  Decode: after the clamped u1, u2 (v1, v2) of the map
+ * below are formed, MIRROR_X: (u1, u2) <- (tw - u2, tw - u1), MIRROR_Y: (v1, v2) <- (th - v2, th - v1), each
+ * subtraction one rounded fp32 operation; the edge test runs on the new values (the edge bits name sides of the window
+ * in source orientation), then + x0 / + y0.  Tables with both bits clear render and decode as before. */
+#define YM_TILE_MIRROR_X 16
+#define YM_TILE_MIRROR_Y 32
 /* src / meta as for ym_letterbox_u8c; out planar (n_tiles, ch, out_h, out_w) fp32.  Tile t is, bit for bit, what
  * ym_letterbox_u8c writes for a stand-alone image holding exactly the window's pixels with the entry {nw, nh, left,
  * top, w0 = tw, h0 = th}: the resize taps clamp at the window's last row and column, not at the image's, and
@@ -629,6 +639,8 @@ int ym_slice_letterbox_u8c(const uint8_t* src, const int64_t* meta, int n_images
  *               frame pixels
  *   map         fp32, every step rounded: u = min(max((x - left) * sx, 0), tw), X = u + x0; v, Y likewise from top,
  *               sy, th, y0
+ *   mirror      YM_TILE_MIRROR_X: (u1, u2) <- (tw - u2, tw - u1); YM_TILE_MIRROR_Y: (v1, v2) <- (th - v2, th - v1), before
+ *               the edge test and before + x0 / + y0 (see the bits above)
  *   edge > 0    a candidate is dropped when (edges & 1) && u1 < edge, (edges & 2) && u2 > tw - edge,
  *               (edges & 4) && v1 < edge or (edges & 8) && v2 > th - edge: a tile border cuts it, and the overlap
  *               lets a neighbouring tile see it whole
@@ -666,6 +678,28 @@ size_t ym_decode_nmm_tiles_workspace_size(int64_t G, int64_t R, int class_aware)
 int ym_decode_nmm_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride, int64_t tile_stride,
                         int64_t col_stride, const ym_tile_entry* table_dev, const int64_t* tile_begin, int64_t G,
                         float conf, float match_thr, int metric, int merge, float edge, int class_aware, int max_det,
+                        void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
+                        float* out_scores, int64_t* out_labels, int64_t* out_index, int64_t* out_row,
+                        int32_t* out_merged, void* stream);
+/* Decode + greedy merging with a score-weighted MEAN box ("weighted NMS" / box voting, the merge of several
+ * estimates of one whole box, as the views of test-time augmentation give them).  The arguments are those of
+ * ym_decode_nmm_tiles without `merge`; candidates, order, metric, greedy loop (always against the head's own stored
+ * box), max_det and every output but out_boxes are as there.  out_boxes: a head that absorbed nothing keeps its stored
+ * box, bit for bit; otherwise, per corner coordinate j over the head and everything it absorbed,
+ *   q_i  = max(1, llrint(min(max(score_i, 0), 1) * 2^12))
+ *   c_ij = llrint(min(max(coord_ij, -2^20), 2^20) * 2^5)
+ *   out_j = fp32(fp64(sum_i q_i c_ij) / (fp64(sum_i q_i) * 2^5))
+ * with both sums exact in int64 (integer atomics: no dependence on arrival order, no float atomic).  No accepted call
+ * can overflow: |q c| <= 2^37 and fewer than 2^26 terms.  |out_j - the fp64 weighted mean of the fp32 inputs| <=
+ * 2^-6 + D eta / (1 - eta) + 2^-24 |mean|, D the cluster's spread in that coordinate, eta = 2^-13 / conf, for scores in
+ * (conf, 1] and coordinates within the clamp (derived in DESIGN §27).
+ * YM_ERR_ARG before any launch: whatever ym_decode_nmm_tiles refuses, and R >= 2^26.
+ * Workspace: ym_decode_nmw_tiles_workspace_size (callable without a GPU); the accumulators live there and need no
+ * memset. */
+size_t ym_decode_nmw_tiles_workspace_size(int64_t G, int64_t R, int class_aware);
+int ym_decode_nmw_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride, int64_t tile_stride,
+                        int64_t col_stride, const ym_tile_entry* table_dev, const int64_t* tile_begin, int64_t G,
+                        float conf, float match_thr, int metric, float edge, int class_aware, int max_det,
                         void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_boxes,
                         float* out_scores, int64_t* out_labels, int64_t* out_index, int64_t* out_row,
                         int32_t* out_merged, void* stream);

@@ -208,7 +208,8 @@ YM_HD static inline void ym_lb_sample_c(const uint8_t* src, const int64_t* meta,
 
 /* ---------------------------------------------------------------- tiles (ym_slice_letterbox_u8c)
  * A tile is a tw x th window of a wider image: its rows lie `pitch` bytes apart, and everything else is the
- * letterbox of a stand-alone tw x th image, so the second taps clamp at the window's last column and row. */
+ * letterbox of a stand-alone tw x th image, so the second taps clamp at the window's last column and row.
+ * YM_TILE_MIRROR_X / _Y (yolomi.h) reverse the columns / rows of the rendered nw x nh rectangle. */
 
 /* ym_aug_set_taps for the th x tw window at `win` whose rows are `pitch` bytes apart */
 YM_HD static inline void ym_aug_set_taps_pitch(const uint8_t* win, int th, int tw, int ch, int64_t pitch, int sx,
@@ -231,11 +232,14 @@ YM_HD static inline bool ym_tile_valid(const int64_t* meta, int n_images, const 
 /* ym_slice_letterbox_u8c: the `ch` values v[0..ch) of frame pixel (x, y) of the tile `e` describes */
 YM_HD static inline void ym_tile_sample_c(const uint8_t* src, const int64_t* meta, int n_images, int ch,
                                           const ym_tile_entry* e, int fill, int x, int y, int* v) {
-    const int64_t u = int64_t(x) - e->left, w = int64_t(y) - e->top;
+    int64_t u = int64_t(x) - e->left, w = int64_t(y) - e->top;
     if (!ym_tile_valid(meta, n_images, e) || u < 0 || u >= e->nw || w < 0 || w >= e->nh) {
         for (int c = 0; c < ch; ++c) v[c] = fill & 255;
         return;
     }
+    /* mirrored views: only the column / row index that feeds the copy and the coefficients is reflected */
+    if (e->edges & YM_TILE_MIRROR_X) u = int64_t(e->nw) - 1 - u;
+    if (e->edges & YM_TILE_MIRROR_Y) w = int64_t(e->nh) - 1 - w;
     const int64_t pitch = meta[3 * int64_t(e->src) + 2] * ch;
     const uint8_t* win = src + meta[3 * int64_t(e->src)] + e->y0 * pitch + int64_t(e->x0) * ch;
     if (e->nw == e->tw && e->nh == e->th) {

@@ -280,13 +280,34 @@ __device__ void bitonic(uint64_t* keys, int P) {
 // out_boxes row by integer min / max atomics on ord_bits images.  Nothing is reduced inside the serial loop, and min,
 // max and integer adds do not depend on the order in which lanes arrive.  The METRIC = IoU, MERGE = false instances
 // are the suppression kernels of before, instruction for instruction.
-template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t, int METRIC = YM_MATCH_IOU, bool MERGE = false>
+//
+// MEAN (ym_decode_nmw_tiles; MERGE instances only, do_union unused): the head's out_boxes row becomes the
+// score-weighted mean of the head and what it absorbed, in fixed point.  The thread that writes kept row k stores the
+// head's own terms (q, q c_x1, q c_y1, q c_x2, q c_y2) into acc[5 (base + k) ..]; the absorbed candidates add theirs
+// by 64-bit integer atomics in the pass that counts out_merged; a head whose weight sum is still its own q absorbed
+// nothing (every q >= 1) and keeps the box as stored.  Integer sums do not depend on the order of arrival.
+constexpr int NMW_QS = 12;                 // score -> weight q in [1, 2^12]
+constexpr int NMW_CS = 5;                  // coordinate -> c in 1/32 pixel, |c| <= 2^25
+constexpr float NMW_CMAX = 1048576.0f;     // |coord| clamp, 2^20: |q c| <= 2^37, and R < 2^26 terms stay below 2^63
+constexpr int64_t NMW_MAX_R = int64_t(1) << 26;
+
+__device__ __forceinline__ long long nmw_q(float score) {
+    const long long q = llrintf(fminf(fmaxf(score, 0.0f), 1.0f) * float(1 << NMW_QS));
+    return q < 1 ? 1 : q;
+}
+__device__ __forceinline__ long long nmw_c(float v) {
+    return llrintf(fminf(fmaxf(v, -NMW_CMAX), NMW_CMAX) * float(1 << NMW_CS));
+}
+
+template <bool SORT_ONLY, bool CLS = false, typename LT = int32_t, int METRIC = YM_MATCH_IOU, bool MERGE = false,
+          bool MEAN = false>
 __global__ void __launch_bounds__(NMS_THREADS)
 nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h, int clamp_norm, Ws w,
                  int32_t* __restrict__ out_count, float* __restrict__ out_boxes, float* __restrict__ out_scores,
                  int64_t* __restrict__ out_labels, int64_t* __restrict__ out_index,
                  const LT* __restrict__ labs = nullptr, int max_det = 0, int32_t* __restrict__ out_merged = nullptr,
-                 int do_union = 0) {
+                 int do_union = 0, long long* __restrict__ acc = nullptr) {
+    static_assert(!MEAN || MERGE, "the mean is formed in the MERGE pass");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint64_t* skeys = reinterpret_cast<uint64_t*>(smem);            // SORT_LDS_KEYS
     __shared__ int sh[NMS_WAVES + 1];
@@ -469,7 +490,12 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
             bx.w = fminf(fmaxf(bx.w / img_h, 0.0f), 1.0f);
         }
         int64_t o = base + k;
-        if (MERGE && do_union)                  // the union pass works on the order-preserving integer images
+        if constexpr (MEAN) {                   // the head's own terms; the absorbed add theirs below
+            const long long q = nmw_q(w.score[row]);
+            long long* a = acc + 5 * o;
+            a[0] = q, a[1] = q * nmw_c(bx.x), a[2] = q * nmw_c(bx.y), a[3] = q * nmw_c(bx.z), a[4] = q * nmw_c(bx.w);
+        }
+        if (!MEAN && MERGE && do_union)         // the union pass works on the order-preserving integer images
             reinterpret_cast<uint4*>(out_boxes)[o] = make_uint4(ord_bits(bx.x), ord_bits(bx.y), ord_bits(bx.z),
                                                                 ord_bits(bx.w));
         else
@@ -487,7 +513,49 @@ nms_image_kernel(int64_t N, int64_t KP, float iou_thr, float img_w, float img_h,
     // through) before the atomics, which run in L2, and the rows are read back by agent-scope atomic loads, never
     // through this CU's vector cache.  A coordinate that cannot move
     // its head's (min and max are monotone: the test may use a stale value safely) costs a load, not an atomic.
-    if constexpr (MERGE) {
+    if constexpr (MEAN) {
+        __syncthreads();
+        using ull = unsigned long long;
+        // (two's complement: the unsigned add is the signed one)
+        auto fold = [&](int k, float4 bx, float score) {      // 0 <= k < nk: the slot of a kept head
+            if (out_merged) atomicAdd(&out_merged[base + k], 1);
+            const long long q = nmw_q(score);
+            ull* a = reinterpret_cast<ull*>(acc + 5 * (base + k));
+            atomicAdd(a + 0, ull(q));
+            atomicAdd(a + 1, ull(q * nmw_c(bx.x)));
+            atomicAdd(a + 2, ull(q * nmw_c(bx.y)));
+            atomicAdd(a + 3, ull(q * nmw_c(bx.z)));
+            atomicAdd(a + 4, ull(q * nmw_c(bx.w)));
+        };
+        if (in_regs) {
+#pragma unroll
+            for (int it = 0; it < REG_ITEMS; ++it)
+                if (slot[it] >= 0) {
+                    const int f = int(uint32_t(keys[tid + it * NMS_THREADS]));
+                    fold(slot[it], mybox[it], w.score[base + w.frow[base + f]]);
+                }
+        } else {
+            for (int s = tid; s < K; s += NMS_THREADS) {
+                const int32_t g = galive[s];
+                if (g < 0) {
+                    const int64_t row = base + w.frow[base + int(uint32_t(keys[s]))];
+                    fold(-g - 1, w.box[row], w.score[row]);
+                }
+            }
+        }
+        __syncthreads();
+        auto cur = [&](const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+        for (int k = tid; k < nk; k += NMS_THREADS) {
+            const int64_t o = base + k;
+            const long long* a = acc + 5 * o;
+            const long long sq = cur(a);
+            if (sq == nmw_q(out_scores[o])) continue;           // absorbed nothing: the stored box stands
+            const double den = double(sq) * double(1 << NMW_CS);
+            reinterpret_cast<float4*>(out_boxes)[o] =
+                make_float4(float(double(cur(a + 1)) / den), float(double(cur(a + 2)) / den),
+                            float(double(cur(a + 3)) / den), float(double(cur(a + 4)) / den));
+        }
+    } else if constexpr (MERGE) {
         if (!do_union && !out_merged) return;
         __syncthreads();
         uint32_t* ub = reinterpret_cast<uint32_t*>(out_boxes) + base * 4;
@@ -1048,10 +1116,20 @@ __device__ __forceinline__ void tile_candidate(const ym_tile_entry& e, float x, 
                                                int lab, float conf, float edge, int64_t o, const Ws& w) {
     const float hw = bw / 2.0f, hh = bh / 2.0f;
     const float left = float(e.left), top = float(e.top), tw = float(e.tw), th = float(e.th);
-    const float u1 = fminf(fmaxf(__fmul_rn(__fsub_rn(x - hw, left), e.sx), 0.f), tw);
-    const float v1 = fminf(fmaxf(__fmul_rn(__fsub_rn(y - hh, top), e.sy), 0.f), th);
-    const float u2 = fminf(fmaxf(__fmul_rn(__fsub_rn(x + hw, left), e.sx), 0.f), tw);
-    const float v2 = fminf(fmaxf(__fmul_rn(__fsub_rn(y + hh, top), e.sy), 0.f), th);
+    float u1 = fminf(fmaxf(__fmul_rn(__fsub_rn(x - hw, left), e.sx), 0.f), tw);
+    float v1 = fminf(fmaxf(__fmul_rn(__fsub_rn(y - hh, top), e.sy), 0.f), th);
+    float u2 = fminf(fmaxf(__fmul_rn(__fsub_rn(x + hw, left), e.sx), 0.f), tw);
+    float v2 = fminf(fmaxf(__fmul_rn(__fsub_rn(y + hh, top), e.sy), 0.f), th);
+    // mirrored views: back through the mirror in window pixels, before the edge test, whose bits name
+    // window sides in source orientation
+    if (e.edges & YM_TILE_MIRROR_X) {
+        const float a = __fsub_rn(tw, u2), b = __fsub_rn(tw, u1);
+        u1 = a, u2 = b;
+    }
+    if (e.edges & YM_TILE_MIRROR_Y) {
+        const float a = __fsub_rn(th, v2), b = __fsub_rn(th, v1);
+        v1 = a, v2 = b;
+    }
     bool cut = false;
     if (edge > 0.0f)
         cut = ((e.edges & 1) && u1 < edge) || ((e.edges & 2) && u2 > __fsub_rn(tw, edge)) ||
@@ -1148,8 +1226,25 @@ void launch_nmm_instance(bool track, int64_t G, int64_t R, float match_thr, Ws w
                            out_scores, out_labels, out_index, labs, max_det, static_cast<int32_t*>(nullptr), 0);
 }
 
-// nmm: ym_decode_nmm_tiles (fn names the entry point in messages); otherwise metric = IoU, merge = 0, out_merged null
-int decode_tiles_impl(const char* fn, bool nmm, const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
+// the weighted-mean instances (ym_decode_nmw_tiles); acc: G * R * 5 sums in the workspace
+template <bool CLS, int METRIC>
+void launch_nmw_instance(int64_t G, int64_t R, float match_thr, Ws w, int32_t* out_count, float* out_boxes,
+                         float* out_scores, int64_t* out_labels, int64_t* out_index, int max_det, int32_t* out_merged,
+                         long long* acc, hipStream_t st) {
+    const size_t lds = size_t(SORT_LDS_KEYS) * sizeof(uint64_t);
+    const int32_t* labs = CLS ? static_cast<const int32_t*>(w.label) : nullptr;
+    hipLaunchKernelGGL((nms_image_kernel<false, CLS, int32_t, METRIC, true, true>), dim3(unsigned(G)),
+                       dim3(NMS_THREADS), lds, st, R, pow2_at_least(R), match_thr, 1.0f, 1.0f, 0, w, out_count,
+                       out_boxes, out_scores, out_labels, out_index, labs, max_det, out_merged, 0, acc);
+}
+
+inline size_t nmw_ws_bytes(int64_t G, int64_t R) {
+    return tiles_ws_bytes(G, R) + align256(size_t(G) * size_t(R) * 5 * sizeof(long long));
+}
+
+// nmm: ym_decode_nmm_tiles / ym_decode_nmw_tiles (fn names the entry point in messages); otherwise metric = IoU,
+// merge = 0, out_merged null.  mean: ym_decode_nmw_tiles (merge unused)
+int decode_tiles_impl(const char* fn, bool nmm, bool mean, const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
                       int64_t tile_stride, int64_t col_stride, const ym_tile_entry* table_dev,
                       const int64_t* tile_begin, int64_t G, float conf, float thr, int metric, int merge, float edge,
                       int class_aware, int max_det, void* workspace, size_t workspace_bytes, int32_t* out_count,
@@ -1174,13 +1269,14 @@ int decode_tiles_impl(const char* fn, bool nmm, const float* pred, int64_t T, in
     YM_CHECK_ARG(tile_begin[G] <= T, "%s: tile_begin[G]=%lld > T=%lld", fn, (long long)tile_begin[G], (long long)T);
     const int64_t R = N * most;                              // < 2^61: both factors were bounded above
     YM_CHECK_ARG(R < (int64_t(1) << 30), "%s: R=%lld too large", fn, (long long)R);
+    YM_CHECK_ARG(!mean || R < NMW_MAX_R, "%s: R=%lld too large for the int64 sums (< 2^26)", fn, (long long)R);
     if (G == 0) return YM_OK;
     YM_CHECK_ARG(out_count, "%s: out_count is NULL", fn);
     hipStream_t st = as_stream(stream);
     if (R == 0) return hipMemsetAsync(out_count, 0, G * sizeof(int32_t), st) == hipSuccess ? YM_OK : YM_ERR_HIP;
     YM_CHECK_ARG(pred && table_dev && workspace && out_boxes && out_scores && out_labels && out_index,
                  "%s: NULL argument", fn);
-    const size_t need = tiles_ws_bytes(G, R);
+    const size_t need = mean ? nmw_ws_bytes(G, R) : tiles_ws_bytes(G, R);
     YM_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, workspace_bytes, need);
     Ws w = carve_tiles(workspace, G, R);
     for (int64_t g0 = 0; g0 < G; g0 += TILE_SPAN) {
@@ -1197,7 +1293,22 @@ int decode_tiles_impl(const char* fn, bool nmm, const float* pred, int64_t T, in
     }
     YM_LAUNCH_CHECK("rowmax tiles");
     const bool track = merge != 0 || out_merged != nullptr;
-    if (metric == YM_MATCH_IOU && !track) {                  // the suppression kernels themselves
+    if (mean) {
+        long long* acc = reinterpret_cast<long long*>(static_cast<char*>(workspace) + tiles_ws_bytes(G, R));
+        if (class_aware && metric == YM_MATCH_IOS)
+            launch_nmw_instance<true, YM_MATCH_IOS>(G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                    out_index, max_det, out_merged, acc, st);
+        else if (class_aware)
+            launch_nmw_instance<true, YM_MATCH_IOU>(G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                    out_index, max_det, out_merged, acc, st);
+        else if (metric == YM_MATCH_IOS)
+            launch_nmw_instance<false, YM_MATCH_IOS>(G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                     out_index, 0, out_merged, acc, st);
+        else
+            launch_nmw_instance<false, YM_MATCH_IOU>(G, R, thr, w, out_count, out_boxes, out_scores, out_labels,
+                                                     out_index, 0, out_merged, acc, st);
+        YM_LAUNCH_CHECK("nms_image_kernel (weighted mean)");
+    } else if (metric == YM_MATCH_IOU && !track) {                  // the suppression kernels themselves
         const int rc = launch_nms(G, R, thr, 1.0f, 1.0f, 0, w, out_count, out_boxes, out_scores, out_labels, out_index,
                                   st, class_aware != 0, max_det);
         if (rc != YM_OK) return rc;
@@ -1239,7 +1350,7 @@ extern "C" int ym_decode_nms_tiles(const float* pred, int64_t T, int64_t N, int6
                                    int class_aware, int max_det, void* workspace, size_t workspace_bytes,
                                    int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels,
                                    int64_t* out_index, int64_t* out_row, void* stream) {
-    return decode_tiles_impl("ym_decode_nms_tiles", false, pred, T, N, C, row_stride, tile_stride, col_stride,
+    return decode_tiles_impl("ym_decode_nms_tiles", false, false, pred, T, N, C, row_stride, tile_stride, col_stride,
                              table_dev, tile_begin, G, conf, iou_thr, YM_MATCH_IOU, 0, edge, class_aware, max_det,
                              workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
                              out_row, nullptr, stream);
@@ -1257,8 +1368,26 @@ extern "C" int ym_decode_nmm_tiles(const float* pred, int64_t T, int64_t N, int6
                                    size_t workspace_bytes, int32_t* out_count, float* out_boxes, float* out_scores,
                                    int64_t* out_labels, int64_t* out_index, int64_t* out_row, int32_t* out_merged,
                                    void* stream) {
-    return decode_tiles_impl("ym_decode_nmm_tiles", true, pred, T, N, C, row_stride, tile_stride, col_stride,
+    return decode_tiles_impl("ym_decode_nmm_tiles", true, false, pred, T, N, C, row_stride, tile_stride, col_stride,
                              table_dev, tile_begin, G, conf, match_thr, metric, merge, edge, class_aware, max_det,
+                             workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
+                             out_row, out_merged, stream);
+}
+
+// (ym_decode_nms_tiles's workspace, then the 5 int64 sums of every output slot)
+extern "C" size_t ym_decode_nmw_tiles_workspace_size(int64_t G, int64_t R, int class_aware) {
+    (void)class_aware;
+    return nmw_ws_bytes(std::max<int64_t>(G, 0), std::max<int64_t>(R, 1));
+}
+
+extern "C" int ym_decode_nmw_tiles(const float* pred, int64_t T, int64_t N, int64_t C, int64_t row_stride,
+                                   int64_t tile_stride, int64_t col_stride, const ym_tile_entry* table_dev,
+                                   const int64_t* tile_begin, int64_t G, float conf, float match_thr, int metric,
+                                   float edge, int class_aware, int max_det, void* workspace, size_t workspace_bytes,
+                                   int32_t* out_count, float* out_boxes, float* out_scores, int64_t* out_labels,
+                                   int64_t* out_index, int64_t* out_row, int32_t* out_merged, void* stream) {
+    return decode_tiles_impl("ym_decode_nmw_tiles", true, true, pred, T, N, C, row_stride, tile_stride, col_stride,
+                             table_dev, tile_begin, G, conf, match_thr, metric, 0, edge, class_aware, max_det,
                              workspace, workspace_bytes, out_count, out_boxes, out_scores, out_labels, out_index,
                              out_row, out_merged, stream);
 }

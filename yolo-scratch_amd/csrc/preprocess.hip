@@ -223,6 +223,50 @@ __global__ void letterbox_u8c_kernel(const uint8_t* __restrict__ src, const int6
 // blockIdx.y walks tiles, so the entry, its validity, the window's first byte and the copy / resize choice are
 // block-uniform.  The window is addressed as an image whose rows lie the source's pitch apart; a tile that is not valid
 // (ym_tile_valid) takes the fill and touches no source byte, so a wrong table cannot cause a read outside an image.
+// The pixel groups of one tile.  MIR: a mirrored view (YM_TILE_MIRROR_X / _Y): the column / row index that
+// feeds the copy and the coefficients is reflected inside the rectangle.  The choice is made once per tile, outside
+// the pixel loop, so tables without the bits run the loop they ran before the bits existed.
+template <int CH, bool MIR>
+__device__ __forceinline__ void slice_tile_groups(const ym_tile_entry& e, bool valid, bool copy, const uint8_t* win,
+                                                  int64_t pitch, double fx, double fy, int W, int HW, int groups,
+                                                  float fill, int vec, float* __restrict__ o) {
+    [[maybe_unused]] const bool mir_x = (e.edges & YM_TILE_MIRROR_X) != 0, mir_y = (e.edges & YM_TILE_MIRROR_Y) != 0;
+    [[maybe_unused]] const int64_t ulast = int64_t(e.nw) - 1, wlast = int64_t(e.nh) - 1;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        const int p = g << 2;
+        int y = p / W, x = p - y * W;
+        float v[CH][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int64_t u = int64_t(x) - e.left, w = int64_t(y) - e.top;
+            if (p + k < HW && valid && u >= 0 && u < e.nw && w >= 0 && w < e.nh) {
+                if constexpr (MIR) {
+                    u = mir_x ? ulast - u : u;
+                    w = mir_y ? wlast - w : w;
+                }
+                if (copy) {
+                    const uint8_t* px = win + w * pitch + u * CH;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) v[c][k] = float(px[c]) / 255.0f;
+                } else {
+                    int sx, a0, a1, sy, b0, b1;
+                    ym_aug_lin_coeff(int(u), fx, e.tw, sx, a0, a1);
+                    ym_aug_lin_coeff(int(w), fy, e.th, sy, b0, b1);
+                    ym_aug_taps tp;
+                    ym_aug_set_taps_pitch(win, e.th, e.tw, CH, pitch, sx, a0, a1, sy, b0, b1, tp);
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) v[c][k] = float(ym_aug_taps_value(tp, c)) / 255.0f;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CH; ++c) v[c][k] = fill;
+            }
+            if (++x == W) { x = 0; ++y; }
+        }
+        store_planes<CH>(o, HW, p, vec, v);
+    }
+}
+
 template <int CH>
 __global__ void slice_letterbox_u8c_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ meta,
                                            int n_images, const ym_tile_entry* __restrict__ table, int n_tiles, int H,
@@ -241,35 +285,10 @@ __global__ void slice_letterbox_u8c_kernel(const uint8_t* __restrict__ src, cons
         }
         const double fx = valid ? double(e.tw) / e.nw : 0.0, fy = valid ? double(e.th) / e.nh : 0.0;
         float* o = out + int64_t(t) * CH * HW;
-        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
-            const int p = g << 2;
-            int y = p / W, x = p - y * W;
-            float v[CH][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int64_t u = int64_t(x) - e.left, w = int64_t(y) - e.top;
-                if (p + k < HW && valid && u >= 0 && u < e.nw && w >= 0 && w < e.nh) {
-                    if (copy) {
-                        const uint8_t* px = win + w * pitch + u * CH;
-#pragma unroll
-                        for (int c = 0; c < CH; ++c) v[c][k] = float(px[c]) / 255.0f;
-                    } else {
-                        int sx, a0, a1, sy, b0, b1;
-                        ym_aug_lin_coeff(int(u), fx, e.tw, sx, a0, a1);
-                        ym_aug_lin_coeff(int(w), fy, e.th, sy, b0, b1);
-                        ym_aug_taps tp;
-                        ym_aug_set_taps_pitch(win, e.th, e.tw, CH, pitch, sx, a0, a1, sy, b0, b1, tp);
-#pragma unroll
-                        for (int c = 0; c < CH; ++c) v[c][k] = float(ym_aug_taps_value(tp, c)) / 255.0f;
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < CH; ++c) v[c][k] = fill;
-                }
-                if (++x == W) { x = 0; ++y; }
-            }
-            store_planes<CH>(o, HW, p, vec, v);
-        }
+        if (e.edges & (YM_TILE_MIRROR_X | YM_TILE_MIRROR_Y))            // block-uniform, like everything of the entry
+            slice_tile_groups<CH, true>(e, valid, copy, win, pitch, fx, fy, W, HW, groups, fill, vec, o);
+        else
+            slice_tile_groups<CH, false>(e, valid, copy, win, pitch, fx, fy, W, HW, groups, fill, vec, o);
     }
 }
 

@@ -5,6 +5,8 @@
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source orbital_frames/ --slice 640 --slice-edge 4
     python yolo-scratch_amd/predict.py --weights runs/best.pt --source orbital_frames/ --slice 640 --slice-merge nmm \
         --slice-metric ios
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --ch 3 --nc 80 --tta --slice-merge mean
+    python yolo-scratch_amd/predict.py --weights runs/best.pt --source photos/ --tta-views 1,0.83:lr,0.67:ud
 
 Per image `<save-dir>/<stem>.txt` with rows `cls cx cy w h conf` normalised to the source image (the label format of
 datasets/yolo_txt.py plus the confidence), and one `<save-dir>/predictions.json` with the pixel boxes.  The images
@@ -53,12 +55,19 @@ def build_parser():
                     help="skip the extra pass over the whole image (it sees objects larger than a window)")
     ap.add_argument("--slice-edge", type=float, default=0.0,
                     help="drop a window's boxes within this many pixels of a window side inside the image (0: none)")
-    ap.add_argument("--slice-merge", type=str, default="nms", choices=["nms", "nmm"],
-                    help="how a sliced image's boxes are joined: nms suppresses what overlaps a kept box, nmm merges "
-                         "it into the kept box, which becomes the union (--iou is the match threshold)")
+    ap.add_argument("--slice-merge", type=str, default="nms", choices=["nms", "nmm", "mean"],
+                    help="how the boxes of an image's windows and views are joined: nms suppresses what overlaps a kept "
+                         "box, nmm merges it into the kept box, which becomes the union, mean merges it and the kept "
+                         "box becomes the score-weighted mean, the merge for --tta (--iou is the match threshold)")
     ap.add_argument("--slice-metric", type=str, default="iou", choices=["iou", "ios"],
                     help="the overlap --iou is compared with: iou, or ios, the intersection over the smaller box, "
                          "which joins a box cut by a window border to its whole twin")
+    ap.add_argument("--tta", action="store_true",
+                    help="test-time augmentation: run every image (or window of --slice) at scales 1 / 0.83 / 0.67, the "
+                         "middle view mirrored left-right, and join the views' boxes per image (not with --rect)")
+    ap.add_argument("--tta-views", type=str, default=None, metavar="SPEC",
+                    help="the views of --tta (which it implies): comma-separated scale[:flip], 0 < scale <= 1, flip lr, "
+                         "ud or lrud, e.g. 1,0.83:lr,0.67")
     ap.add_argument("--save-dir", type=str, default="runs/predict")
     return ap
 
@@ -70,8 +79,21 @@ def parse_args(argv=None):
         ap.error("--slice is a window size in pixels")
     if args.slice and args.rect:
         ap.error("--slice and --rect exclude each other")
-    if (args.slice_merge, args.slice_metric) != ("nms", "iou") and not args.slice:
-        ap.error("--slice-merge and --slice-metric need --slice")
+    args.views = None
+    if args.tta_views is not None:
+        from datasets.tta import parse_views
+        try:
+            args.views = parse_views(args.tta_views)
+        except ValueError as e:
+            ap.error(f"--tta-views: {e}")
+        args.tta = True
+    elif args.tta:
+        from datasets.tta import DEFAULT_VIEWS
+        args.views = list(DEFAULT_VIEWS)
+    if args.tta and args.rect:
+        ap.error("--tta and --rect exclude each other")
+    if (args.slice_merge, args.slice_metric) != ("nms", "iou") and not args.slice and not args.tta:
+        ap.error("--slice-merge and --slice-metric need --slice or --tta")
     return args
 
 
@@ -129,7 +151,7 @@ def main(argv=None):
     predictor = Predictor(model, imgsz=args.imgsz, ch=args.ch, conf=args.conf, iou=args.iou, max_det=args.max_det,
                           class_aware=True, device=device, batch=args.batch, rect=args.rect, slice=args.slice,
                           slice_overlap=args.slice_overlap, slice_full=args.slice_full, slice_edge=args.slice_edge,
-                          slice_merge=args.slice_merge, slice_metric=args.slice_metric)
+                          slice_merge=args.slice_merge, slice_metric=args.slice_metric, tta=args.views)
     save_dir = Path(args.save_dir)
     save_dir.mkdir(parents=True, exist_ok=True)
     order = list(range(len(files)))

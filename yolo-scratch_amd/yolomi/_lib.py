@@ -216,6 +216,9 @@ SIGNATURES = {
     "ym_decode_nmm_tiles_workspace_size": (SZ, [I64, I64, INT]),
     "ym_decode_nmm_tiles": (R, [P, I64, I64, I64, I64, I64, I64, P, P, I64, F32, F32, INT, INT, F32, INT, INT, P, SZ, P,
                                 P, P, P, P, P, P, P]),
+    "ym_decode_nmw_tiles_workspace_size": (SZ, [I64, I64, INT]),
+    "ym_decode_nmw_tiles": (R, [P, I64, I64, I64, I64, I64, I64, P, P, I64, F32, F32, INT, F32, INT, INT, P, SZ, P, P,
+                                P, P, P, P, P, P]),
     "ym_grad_norm_blocks": (R, [I64]),
     "ym_grad_norm": (R, [P, INT, I64, P, P, P]),
     "ym_adamw": (R, [P, INT, I64, F64, F64, F64, F64, F64, I64, F32, P, P]),

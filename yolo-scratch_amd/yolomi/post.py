@@ -130,6 +130,18 @@ def decode_nmm_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, co
                          (METRICS[metric], int(bool(merge))))
 
 
+def decode_nmw_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, conf: float, thr: float,
+                     metric: str = "iou", class_aware: bool = False, max_det: int = 0, edge: float = 0.0):
+    """Decode + greedy merging with a score-weighted mean box (ym_decode_nmw_tiles): everything of
+    decode_nmm_tiles but "boxes", where a kept box that absorbed candidates holds the score-weighted mean of itself
+    and what it absorbed, formed in fixed point on integer sums (order-independent, bit for bit reproducible); a kept
+    box that absorbed nothing is unchanged.  The merge for several estimates of one whole box, as the views of
+    test-time augmentation give them."""
+    if metric not in METRICS:
+        raise ValueError(f"decode_nmw_tiles: metric is 'iou' or 'ios', got {metric!r}")
+    return _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, edge, (METRICS[metric], "mean"))
+
+
 def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, conf: float, iou_thr: float,
                      class_aware: bool = False, max_det: int = 0, edge: float = 0.0):
     """Decode + NMS of sliced inference (ym_decode_nms_tiles): pred read as (T, N, 4+C), one slice per
@@ -145,7 +157,8 @@ def decode_nms_tiles(pred: torch.Tensor, table_dev: torch.Tensor, tile_begin, co
 
 
 def _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, edge, nmm):
-    """nmm: None (ym_decode_nms_tiles) or (metric, merge) (ym_decode_nmm_tiles, which also fills "merged")."""
+    """nmm: None (ym_decode_nms_tiles), (metric, merge) (ym_decode_nmm_tiles, which also fills "merged") or
+    (metric, "mean") (ym_decode_nmw_tiles)."""
     import ctypes
     from ._lib import TileEntry, lib
     require_device(pred, table_dev)
@@ -165,7 +178,9 @@ def _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, 
     most = max([b - a for a, b in zip(begin, begin[1:])] + [0])
     R = max(N * most, 0)
     cb = (ctypes.c_int64 * (G + 1))(*begin)
-    ws_bytes = lib().ym_decode_nms_tiles_workspace_size(G, max(R, 1), int(class_aware))
+    mean = nmm is not None and nmm[1] == "mean"
+    size_fn = lib().ym_decode_nmw_tiles_workspace_size if mean else lib().ym_decode_nms_tiles_workspace_size
+    ws_bytes = size_fn(G, max(R, 1), int(class_aware))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     cnt = torch.empty(G, dtype=torch.int32, device=dev)          # every count is written by the launch
     boxes = torch.empty(G, R, 4, dtype=torch.float32, device=dev)
@@ -178,6 +193,12 @@ def _decode_tiles(pred, table_dev, tile_begin, conf, thr, class_aware, max_det, 
         call("ym_decode_nms_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
              float(conf), float(thr), float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes, ptr(cnt),
              ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), stream_ptr(dev))
+    elif mean:
+        out["merged"] = torch.empty(G, R, dtype=torch.int32, device=dev)
+        call("ym_decode_nmw_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,
+             float(conf), float(thr), nmm[0], float(edge), int(class_aware), int(max_det), ptr(ws), ws_bytes,
+             ptr(cnt), ptr(boxes), ptr(scores), ptr(labels), ptr(index), ptr(rows), ptr(out["merged"]),
+             stream_ptr(dev))
     else:
         out["merged"] = torch.empty(G, R, dtype=torch.int32, device=dev)
         call("ym_decode_nmm_tiles", ptr(p), T, N, C, p.stride(1), p.stride(0), p.stride(2), ptr(table_dev), cb, G,

@@ -18,6 +18,11 @@ frame by ym_slice_letterbox_u8c, `batch` tiles per forward; ym_decode_nms_tiles 
 source pixels and runs one NMS per source image, so there is no unletterbox step.  One host sync per group.
 `slice_merge` / `slice_metric` put ym_decode_nmm_tiles in that NMS's place: greedy merging, matched by the
 IoU or by the intersection over the smaller box.
+
+`tta=VIEWS`: test-time augmentation.  Every window (the whole image, or the tiles of `slice`) is rendered
+once per view (scale, flip) by the same slice kernel, mirrored and reduced on the device from the one upload; the tile
+decode maps every view's boxes back through the mirror, and one merge per image joins the views: the NMS, the greedy
+merge, or `slice_merge="mean"`, ym_decode_nmw_tiles, the score-weighted mean box of every cluster.
 """
 from __future__ import annotations
 
@@ -42,13 +47,17 @@ class Predictor:
     `slice_merge`: "nms" suppresses the tiles' boxes, "nmm" merges them greedily: a kept box absorbs what
     matches it and becomes the union, and the results also carry "merged", the number each box absorbed;
     `slice_metric`: the match value `iou` is compared with, "iou" or "ios" (intersection over the smaller box, which
-    joins a box cut by a tile border to its whole twin).  Both need `slice`."""
+    joins a box cut by a tile border to its whole twin).  "mean" merges as "nmm" does but the kept box becomes the
+    score-weighted mean of what it absorbed (the merge for the views of `tta`).  They need `slice` or `tta`.
+    `tta`: None, True (datasets.tta.DEFAULT_VIEWS: scales 1 / 0.83 / 0.67, the middle view mirrored left-right) or a
+    list of (scale, flip) views, 0 < scale <= 1, flip "", "lr", "ud" or "lrud"; with or without `slice`, not with
+    `rect`."""
 
     def __init__(self, model, imgsz: int = 640, ch: int | None = None, conf: float = 0.25, iou: float = 0.45,
                  max_det: int = 300, class_aware: bool = True, device="cuda", batch: int = 8, fill: int = 114,
                  rect: bool = False, max_frames: int = 8, slice: int = 0, slice_overlap: float = 0.2,
                  slice_full: bool = True, slice_edge: float = 0.0, slice_merge: str = "nms",
-                 slice_metric: str = "iou"):
+                 slice_metric: str = "iou", tta=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise YolomiError("Predictor runs on the MI355X only (no CPU fallback)")
@@ -66,11 +75,18 @@ class Predictor:
         self.slice_full, self.slice_edge = bool(slice_full), float(slice_edge)
         if self.slice < 0:
             raise ValueError("Predictor: slice is a tile size in pixels (0: off)")
-        if slice_merge not in ("nms", "nmm") or slice_metric not in _post.METRICS:
-            raise ValueError(f"Predictor: slice_merge is 'nms' or 'nmm' and slice_metric 'iou' or 'ios', got "
+        self.views = None
+        if tta is not None and tta is not False:
+            from datasets.tta import DEFAULT_VIEWS, check_views
+            self.views = check_views(DEFAULT_VIEWS if tta is True else tta)
+            if rect:
+                raise ValueError("Predictor: tta and rect exclude each other (views run in the imgsz x imgsz frame)")
+        if slice_merge not in ("nms", "nmm", "mean") or slice_metric not in _post.METRICS:
+            raise ValueError(f"Predictor: slice_merge is 'nms', 'nmm' or 'mean' and slice_metric 'iou' or 'ios', got "
                              f"{slice_merge!r}, {slice_metric!r}")
-        if (slice_merge, slice_metric) != ("nms", "iou") and not self.slice:
-            raise ValueError("Predictor: slice_merge and slice_metric belong to sliced inference (slice=TILE)")
+        if (slice_merge, slice_metric) != ("nms", "iou") and not self.slice and self.views is None:
+            raise ValueError("Predictor: slice_merge and slice_metric belong to sliced inference (slice=TILE) and to "
+                             "test-time augmentation (tta=VIEWS)")
         self.slice_merge, self.slice_metric = slice_merge, slice_metric
         if self.slice:
             if rect:
@@ -129,14 +145,19 @@ class Predictor:
     def _run_sliced(self, images):
         """Up to `batch` sources: one upload, the tiles `batch` at a time through the slice kernel and the eval
         forward (the last chunk padded with src = -1 tiles, so the plan and graph of (batch, imgsz, imgsz) replay),
-        every chunk's output copied into one (T, 4 + nc, A) buffer, then one ym_decode_nms_tiles and its sync."""
+        every chunk's output copied into one (T, 4 + nc, A) buffer, then one ym_decode_nms_tiles and its sync.
+        With `tta` the table holds every window once per view (datasets.tta.view_table); nothing else differs."""
         from datasets.crater import pack_images
         from datasets.slicing import slice_batch, tile_bytes, tile_table
         raw = [self._raw(im) for im in images]
         packed = pack_images(raw, self.imgsz, self.ch)
         S, nb = self.imgsz, self.batch
-        table, begin = tile_table(packed["img_meta"][:, 1:].tolist(), self.slice, self.slice_overlap, S,
-                                  self.slice_full)
+        hws = packed["img_meta"][:, 1:].tolist()
+        if self.views is None:
+            table, begin = tile_table(hws, self.slice, self.slice_overlap, S, self.slice_full)
+        else:
+            from datasets.tta import view_table
+            table, begin = view_table(hws, self.views, S, self.slice, self.slice_overlap, self.slice_full)
         T = begin[-1]
         if T == 0:
             z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.device)    # noqa: E731
@@ -158,6 +179,10 @@ class Predictor:
         keys = ("boxes", "scores", "labels")
         if (self.slice_merge, self.slice_metric) == ("nms", "iou"):
             d = _post.decode_nms_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou, **kw)
+        elif self.slice_merge == "mean":
+            d = _post.decode_nmw_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou,
+                                       metric=self.slice_metric, **kw)
+            keys += ("merged",)
         else:
             d = _post.decode_nmm_tiles(ybuf[:T].transpose(1, 2), tdev, begin, self.conf, self.iou,
                                        metric=self.slice_metric, merge=self.slice_merge == "nmm", **kw)
@@ -186,5 +211,5 @@ class Predictor:
             return out
         out = []
         for lo in range(0, len(images), self.batch):
-            out += (self._run_sliced if self.slice else self._run)(images[lo:lo + self.batch])
+            out += (self._run_sliced if self.slice or self.views else self._run)(images[lo:lo + self.batch])
         return out
