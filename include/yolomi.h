@@ -209,7 +209,21 @@ int ym_conv_kernel(const ym_conv_desc* d, int dir, char* name, int name_len);
 /* y = conv(x, w) (+bias), x fp16 NHWC view, w fp16 [cout][kh][kw][cin], k in 1..3; optional per-block
  * channel sum / sum-of-squares partials [ym_conv_fwd_stat_rows(d)][cout] for training BatchNorm
  * (BatchNorm2d batch stats; not together with a bias).  accumulate is not supported for fp16 output
- * (out_f32 = 2). */
+ * (out_f32 = 2).
+ * Bias: only the halo-staged kernel and the 2-stage implicit GEMM have a bias term; a conv with bias skips the direct,
+ * halo-pipelined and pipelined kernels whatever the policies say, and stores fragments (below).
+ * Stores: 16-bit outputs need y_ld, y_bs multiples of 4 and an 8-byte aligned y (fp32: none).  The halo kernel and
+ * the GEMM's 64- / 128-channel tiles store whole 16-byte runs of 8 channels when there is no bias, y_ld, y_bs and
+ * cout are multiples of 8 and y is 16-byte aligned (the GEMM: fp16 only); every other case stores 8-byte fragments
+ * of 4 channels and, for cout % 4 != 0, the last channels one by one.  The pipelined, halo-pipelined and direct
+ * kernels take cout % 8 == 0 only and always store 16-byte runs (dword aligned buffer stores).  Nothing outside
+ * cout's channels is written.
+ * fp16 outputs are clamped to +-65504 before the rounding: an overflow stores 0x7bff / 0xfbff, never infinity (a
+ * NaN accumulator stores -65504).  The statistics are taken from the fp32 accumulator, not from the stored fp16.
+ * accumulate = 1 into bf16 rounds once (bf16(y + v): fragment stores) or twice (bf16(y + bf16(v)): 16-byte stores),
+ * into fp32 it adds exactly.
+ * n = 0 (or oh * ow = 0) returns YM_OK before any launch: y AND the statistics rows keep every bit — a caller that
+ * sums the rows must not read them after an empty batch. */
 int ym_conv_fwd(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, const float* bias,
                 float* stat_sum, float* stat_sq, void* stream);
 /* dx (+)= conv_transpose(dz, w) using the [cin][kh][kw][cout] weight copy.  d is the FORWARD descriptor: dz is the
@@ -300,7 +314,10 @@ typedef struct {
 /* Conv forward + BatchNorm statistics AND their finalize: ym_conv_fwd (stat_sum / stat_sq as there, bias-free,
  * fp16 z) followed by ym_bn_finalize over its rows, with the same outputs.  Where ym_conv_fwd_bn_fused(d) is 1
  * the finalize runs as the conv launch's tail (the last workgroup of each channel tile folds the tile's rows in
- * fp64, fixed order) instead of a second launch; elsewhere the two launches run in order. */
+ * fp64, fixed order) instead of a second launch; elsewhere (the direct and halo-pipelined kernels) the two launches
+ * run in order.  Either way mean = float(S / count) of the fp64 row sums, the tickets at the head of the workspace are
+ * left at zero, and num_batches_tracked goes up by one.  n = 0: as ym_conv_fwd, nothing is launched by the conv; on
+ * the two-launch routes ym_bn_finalize then folds whatever the rows held. */
 int ym_conv_fwd_bn_fused(const ym_conv_desc* d);
 int ym_conv_fwd_bn(const ym_conv_desc* d, const uint16_t* x, const uint16_t* w, void* y, float* stat_sum,
                    float* stat_sq, const ym_bn_fold* bn, void* stream);

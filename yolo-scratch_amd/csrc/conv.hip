@@ -1134,7 +1134,7 @@ extern "C" int ym_conv_set_hpipe(int mode) {
 // wins: direct register-weight kernel (conv_direct.hip) -> halo-staged pipelined 3x3 (conv_hpipe.hip) -> persistent
 // pipelined implicit GEMM (conv_pipe.hip) -> halo-staged 3x3 (conv_halo.hip) -> this file's 2-stage implicit GEMM.
 struct RouteOpts {
-    bool has_bias;       // the direct and halo-pipelined kernels have no bias term: a conv with bias skips them
+    bool has_bias;       // the direct, halo-pipelined and pipelined kernels have no bias term: a conv with bias skips them
     bool inference;      // a forward without BatchNorm statistics: the direct kernel's lower threshold (direct_plan)
 };
 
@@ -1155,7 +1155,7 @@ static ConvRoute conv_route(const ym_conv_desc* d, int dir, const ConvPolicy& po
         r.algo = 3; r.rows = r.direct.grid; r.id = 3000 + r.direct.variant;
     } else if (!o.has_bias && (r.hpipe = hpipe_plan(d, dir, pol)).ok) {
         r.algo = 4; r.rows = r.hpipe.rows; r.id = 4000 + r.hpipe.cfg;
-    } else if ((r.pipe = pipe_plan(d, dir, pol)).ok) {
+    } else if (!o.has_bias && (r.pipe = pipe_plan(d, dir, pol)).ok) {
         r.algo = 2; r.rows = r.pipe.rows; r.id = 2000 + r.pipe.cfg;
     } else if ((r.halo = halo_plan(d, dir, pol)).ok) {
         r.algo = 1; r.rows = r.halo.gx; r.id = 1000 + 100 * r.halo.cfg + std::min(r.halo.TW, 99);
@@ -1177,7 +1177,7 @@ static int route_launch(const ConvRoute& r, const ym_conv_desc* d, int dir, Gemm
     switch (r.algo) {
         case 3: direct_launch(r.direct, d, dir, a.x, a.w, a.y, a.st_sum, a.st_sq, st); break;
         case 4: hpipe_launch(r.hpipe, d, dir, a.x, a.w, a.y, a.st_sum, a.st_sq, st); break;
-        case 2: pipe_launch(r.pipe, d, dir, a.x, a.w, a.y, a.bias, a.st_sum, a.st_sq, st, fold); break;
+        case 2: pipe_launch(r.pipe, d, dir, a.x, a.w, a.y, a.st_sum, a.st_sq, st, fold); break;
         case 1: halo_launch(r.halo, d, dir, a.x, a.w, a.y, a.bias, a.st_sum, a.st_sq, st, fold); break;
         default:
             if (a.st_sum) a.fold = bn_fold_args(fold);
@@ -1272,7 +1272,8 @@ static int conv_fwd_impl(const ym_conv_desc* d, const uint16_t* x, const uint16_
     a.x = x; a.w = w; a.y = y;
     a.bias = bias; a.st_sum = stat_sum; a.st_sq = stat_sq;
     // fp16 z: the register-transposed epilogue with 16-B row stores (round 4; fp32 / bias outputs: fragment stores)
-    a.ep_lds = d->out_f32 == 2 && !bias && d->y_ld % 8 == 0 && d->y_bs % 8 == 0 &&
+    // (whole 8-channel runs: a channel count of 8 j + 4 would store 4 channels past the view, so it stores fragments)
+    a.ep_lds = d->out_f32 == 2 && !bias && d->y_ld % 8 == 0 && d->y_bs % 8 == 0 && d->cout % 8 == 0 &&
                int64_t(d->n) * d->y_bs * 2 < (int64_t(1) << 31) && reinterpret_cast<uintptr_t>(y) % 16 == 0;
     const ConvRoute r = conv_route(d, 0, pol, {bias != nullptr, stat_sum == nullptr});
     if (taken) *taken = r;

@@ -62,7 +62,6 @@ struct PipeArgs {
     const bf16_t* x; int64_t x_bs, x_ld;     // gathered tensor view (elements)
     const bf16_t* w;                          // [Nout][KH][KW][Kin]
     void* y; int64_t y_bs, y_ld;              // output view
-    const float* bias;                        // [Nout] or null
     float* st_sum; float* st_sq;              // [rows][Nout] or null
     int GH, GW, Kin;
     int OH, OW, Nout;
@@ -752,12 +751,12 @@ static void pipe_geometry(PipeArgs& a, const ym_conv_desc* d, int dgrad, const u
 }
 
 int pipe_launch(const PipePlan& p, const ym_conv_desc* d, int dgrad, const uint16_t* x, const uint16_t* w, void* y,
-                const float* bias, float* st_sum, float* st_sq, hipStream_t st, const ym_bn_fold* fold) {
+                float* st_sum, float* st_sq, hipStream_t st, const ym_bn_fold* fold) {
     PipeArgs a{};
     const int bm = kCfg[p.cfg].bm, bn = kCfg[p.cfg].bn;
     pipe_geometry(a, d, dgrad, x, w, y);
     a.out_f32 = dgrad ? 0 : d->out_f32;
-    a.bias = bias; a.st_sum = st_sum; a.st_sq = st_sq;
+    a.st_sum = st_sum; a.st_sq = st_sq;
     a.accumulate = d->accumulate;
     a.ntiles = (a.Nout + bn - 1) / bn;
     a.ncls = a.os == 2 ? 4 : 1;
